@@ -1,7 +1,7 @@
 """Headline benchmark: env steps/s (+ learner train-steps/s) of the Driver ->
 Replay -> return-scan hot path, 64 envs x 84x84x4 uint8 obs per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one vectorised Driver step of 64 synthetic device envs (env frame
 generation, obs stack/transpose into the policy batch, stub policy, action
@@ -10,9 +10,15 @@ mask, Replay insert) plus the train steps the reference's `Ratio(train_ratio /
 step = Replay.sample(B=16, L=65) + Consec window + GAE scan.  The model
 forward/backward is outside the path and is not run.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the Replay-sample gather
-kernel, timed with HIP events on its own stream inside the timed region;
-`cpu_baseline` is the numpy oracle of the same workload on this box's host.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly
+--steps steps (one fenced region), writes the outputs of the last timed step
+if --dump-outputs is given, and prints the line.  `roofline` is for the
+Replay-sample gather kernel, timed with HIP events on its own stream inside the
+timed region.  Everything measured outside the timed region -- the sustained
+window, the other env-action form, fresh batches, the batches-per-launch sweep
+and plain-copy reference, `cpu_baseline` (the numpy oracle of the same workload
+on the host), the dreamer leg, the replicas-only leg of N > 1, the 16 short
+regions of a --steps < 256 run -- runs with --full only.
 """
 import argparse
 import json
@@ -95,8 +101,9 @@ def pin_cpus(width=4):
 
 
 def _is_launcher():
-  """`python bench.py --gpus N` (N > 1) without a launcher re-executes itself
-  under torch.distributed.run: the ranks pin themselves, not this process."""
+  """`python bench.py --gpus N` (N > 1) without a launcher starts its ranks under
+  torch.distributed.run in a child process: the ranks pin themselves, not this
+  process."""
   if 'WORLD_SIZE' in os.environ:
     return False
   gpus = _flag_value('--gpus', '1')
@@ -156,7 +163,7 @@ def parse():
                       '`config.parallelism` and is context, not the headline')
   p.add_argument('--cpu-seconds', type=float, default=15.0)
   p.add_argument('--sustained-seconds', type=float, default=10.0,
-                 help='after the headline region: the same loop for this long (SURVEY 8d asks for '
+                 help='--full: after the headline region, the same loop for this long (SURVEY 8d asks for '
                       'wall-clock rates over >= 10 s windows); reported as `sustained`, 0 = skip')
   p.add_argument('--stamp-every', type=int, default=0,
                  help='dispatch stamps on one sample gather in this many (1 = every gather).  A '
@@ -176,7 +183,7 @@ def parse():
   p.add_argument('--no-cpu-baseline', action='store_true')
   p.add_argument('--no-dreamer-leg', action='store_true',
                  help='skip the short configs[2] run (1M-step uniform replay, latents written back) '
-                      'that the default single-GPU PPO run appends as `workloads.dreamer`')
+                      'that a single-GPU PPO run with --full appends as `workloads.dreamer`')
   p.add_argument('--dreamer-leg-steps', type=int, default=4000)
   p.add_argument('--prefetch', type=int, default=1, help='train batches gathered per launch')
   p.add_argument('--reuse-outputs', type=int, default=0,
@@ -223,8 +230,8 @@ def parse():
                       '(dreamerv3/agent.py:322-331, lhs = x[:, :K]); the write-back still covers every step')
   p.add_argument('--regions', type=int, default=0,
                  help='how many fenced regions of exactly --steps steps are timed back to back; `value` is '
-                      'their median.  0 (default) = 16 when --steps < 256 (a 20-step region lasts 0.3 ms and '
-                      'reads +-30 %% from run to run by itself), else 1')
+                      'their median.  0 (default) = 1; with --full 16 when --steps < 256 (a 20-step region lasts '
+                      '0.3 ms and reads +-30 %% from run to run by itself)')
   p.add_argument('--pin', default='auto', help='CPUs of the stepping thread: auto (default), 0 = leave alone, a-b')
   p.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                  help='N>1: process-group backend (gloo: the control flow on fewer GPUs than ranks)')
@@ -241,6 +248,16 @@ def parse():
                  help='with --parallel-envs: this many envs per worker process (Driver(envs_per_worker=K)); '
                       'auto (default) = as many worker processes as the CPU budget (affinity mask, cgroup '
                       'quota) runs at once, one per env if it allows (the reference\'s form, driver.py:17-25)')
+  p.add_argument('--full', action='store_true',
+                 help='also measure the context outside the timed region: the sustained window, the other '
+                      'env-action form, fresh batches, the batches-per-launch sweep, the CPU baseline, the '
+                      'dreamer leg, replicas-only (N > 1), and 16 regions when --steps < 256 (--regions 0).  '
+                      'Off (default): exactly one timed region of --steps steps and nothing after it')
+  p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                 help='after the timed region: write what the timed path computed in its last step (the last '
+                      'policy batch, the last train step\'s sampled batch and returns) as DIR/<name>.npy in '
+                      'float32 / float64, 64 MB at most (seeded element samples of the larger arrays).  '
+                      'Inputs are seeded: two runs with the same arguments are comparable output for output')
   return p.parse_args()
 
 
@@ -319,6 +336,7 @@ def build_path(args, rank, device):
     outs = {'dyn/deter': deter, 'dyn/stoch': stoch} if dreamer else {}
     return carry, {'action': actions[state['tick'] % 4096]}, outs
 
+  policy.state = state          # (--dump-outputs reads the last policy batch)
   return emb, env, replay, driver, policy
 
 
@@ -328,8 +346,11 @@ def train_steps_local(counters, base, headline):
 
 def launch_ranks(args):
   """`python bench.py --gpus N` without a launcher: start N local ranks, one per
-  GPU, under torch.distributed.run and become that process (rank 0 prints the
-  JSON line).  Reference shape: embodied/jax/internal.py:96-105."""
+  GPU, under torch.distributed.run in a child process and leave with its exit
+  status (rank 0 prints the JSON line).  This process has asked HIP for the
+  device count: it starts a fresh process rather than replacing its own
+  program.  Reference shape: embodied/jax/internal.py:96-105."""
+  import subprocess
   import socket
   backend = args.backend
   have = torch.cuda.device_count()
@@ -343,7 +364,8 @@ def launch_ranks(args):
          f'--nproc-per-node={args.gpus}', '--master-addr', '127.0.0.1', '--master-port', str(port),
          os.path.abspath(__file__), *sys.argv[1:]]
   sys.stdout.flush()
-  os.execv(sys.executable, cmd)
+  rc = subprocess.call(cmd)
+  sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 def main():
@@ -392,6 +414,9 @@ def main():
   assert world == args.gpus, f'--gpus {args.gpus} but WORLD_SIZE={world}'
   rccl_ranks = dist.get_world_size() if use_dist else 1
 
+  # Seeded inputs (the policy's pre-drawn actions, the value and imagination
+  # tensors): the same arguments compute the same outputs run after run.
+  torch.manual_seed(rank)
   emb, env, replay, driver, policy = build_path(args, rank, device)
   driver_ref = [driver if args.parallel_envs else None]     # (read for the line's config only)
   B, T, L = args.batch, args.length, args.consec * args.length + args.context
@@ -429,6 +454,7 @@ def main():
   collectives = {'on': True, 'sliced': 0, 'gathered': 0}
   schedule = {'fences': 0}          # fences at which the ranks compared their exchange schedules (and agreed)
   fresh = {'on': False, 'stream': None}
+  last_train = {}           # the latest train step's batch and returns (--dump-outputs)
 
   def train_step():
     if args.workload == 'dreamer':
@@ -440,7 +466,7 @@ def main():
       batch = next(stream)
       # (both return scans of the train step -- replay (B,T) and imagination
       # (B*K,H+1), agent.py:401-405,464-466 -- in one launch)
-      adv, _ = emb.scans.lambda_returns(
+      adv, tar = emb.scans.lambda_returns(
           [(batch['is_last'], batch['is_terminal'], batch['reward'], None, value, 1 - 1 / 333, 0.95),
            (imag_flags, imag_flags, imag_rew, None, imag_rew, 1 - 1 / 333, 0.95)],
           out=lambda_out[counters['train_steps'] & 1])
@@ -539,6 +565,10 @@ def main():
         mark.record(slice_state['stream'])
         marks.append(mark)
     counters['train_steps'] += args.prefetch
+    if args.dump_outputs:
+      last_train['batch'] = batch
+      last_train['returns'] = ({'return': adv, 'imag_return': tar} if args.workload == 'dreamer'
+                               else {'advantage': adv, 'target': tar})
     return adv
 
   state_keep = []
@@ -671,8 +701,11 @@ def main():
     # instead of 1.6 (two event records), and a 260 us region has nowhere to hide
     # that: with every second gather stamped `value` read 6.5 % lower than with
     # no stamps at all, with one in eight 1-2 % (profiles/r05_ab_stamps.txt).  The
-    # roofline figure of such a run stands on the sustained window's thousands of
-    # stamped launches anyway (`roofline.source`); the regions keep one in eight.
+    # regions keep one in eight, in a plain run as well: its `value` is measured on
+    # the same path as that of --full.  With --full the roofline figure stands on
+    # the sustained window's thousands of stamped launches (`roofline.source`); a
+    # plain run has only the region's few stamps, and prints `roofline: null` when
+    # none of its gathers was stamped.
     stamp_every = 8
   else:
     # No sustained window behind the regions: every second gather is stamped,
@@ -729,9 +762,10 @@ def main():
   # The timed region: EXACTLY --steps steps between two fences (barrier +
   # synchronize), the maximum over ranks.  A region of a few hundred microseconds
   # (the driver's --steps 20) is dominated by the first launch after a fence and
-  # by where its handful of train steps fall: it is then timed --regions times
-  # back to back and `value` is the MEDIAN region (all of them in `regions`).
-  n_regions = args.regions if args.regions > 0 else (16 if args.steps < 256 else 1)
+  # by where its handful of train steps fall: with --full it is then timed
+  # --regions times back to back and `value` is the MEDIAN region (all of them in
+  # `regions`).  A plain run times one region: exactly --steps timed steps.
+  n_regions = args.regions if args.regions > 0 else (16 if args.full and args.steps < 256 else 1)
   fence()
   region_times, region_counts = [], []
   for _ in range(n_regions):
@@ -759,11 +793,15 @@ def main():
   wb_launches, wb_ms, wb_kernel = replay.profile_report('update', reset=True)
   headline = dict(counters)
   was_unmasked = bool(getattr(driver, '_unmasked', False))     # how the timed regions handed actions to the env
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, policy.state.get('policy_batch'), last_train)
+
+  # Everything from here to the line is context outside the timed region: --full only.
 
   # The same loop for >= --sustained-seconds more (the headline region is as
   # long as --steps says; this window is long whatever the caller chose).
   sustained = None
-  if args.sustained_seconds > 0:
+  if args.full and args.sustained_seconds > 0:
     if stamp_every < 16 and args.consec == 1 and not args.no_timer:
       # A short headline region stamps every second gather; the long window that
       # follows holds thousands: one in 16 (a stamp costs the job time, see --stamp-every)
@@ -823,7 +861,7 @@ def main():
   # and the masked pool write rides in the next early-insert launch -- two launches.
   # The stored transitions are the same either way.
   other_env_actions = None
-  if (not use_dist and env is not None and args.sustained_seconds > 0 and not args.no_context
+  if (args.full and not use_dist and env is not None and args.sustained_seconds > 0 and not args.no_context
       and hasattr(env, 'takes_unmasked_actions') and driver._unmasked is not None):
     fence()
     flipped = not was_unmasked
@@ -865,7 +903,7 @@ def main():
   # `out=`: seven fresh batch tensors and two fresh results per train step, as
   # the reference's fresh arrays.
   fresh_batches = None
-  if (not use_dist and args.workload == 'ppo' and args.sustained_seconds > 0 and not args.no_context
+  if (args.full and not use_dist and args.workload == 'ppo' and args.sustained_seconds > 0 and not args.no_context
       and args.prefetch == 1):
     import functools
     fence()
@@ -896,7 +934,7 @@ def main():
   replicas_only = None
   sliced_share = min(1.0, collectives['sliced'] / max(1, counters['train_steps']))
   gather_share = min(1.0, collectives['gathered'] / max(1, counters['train_steps']))
-  if use_dist and args.sustained_seconds > 0:
+  if args.full and use_dist and args.sustained_seconds > 0:
     fence()
     collectives['on'] = False
     r_steps = max(256, int(2.0 / max(elapsed / args.steps, 1e-6)) // 256 * 256)   # same on every rank
@@ -1046,7 +1084,7 @@ def main():
   # one batch of B=16 per launch is the faithful headline), and a plain
   # device-to-device copy of one batch's bytes out of the same pool — what a
   # kernel with no gather structure at all achieves on this box, read cold.
-  if (roofline and rank == 0 and world == 1 and args.consec == 1 and not args.host_envs
+  if (args.full and roofline and rank == 0 and world == 1 and args.consec == 1 and not args.host_envs
       and not args.no_context):
     try:
       replay.profile(True, every=1)
@@ -1080,7 +1118,8 @@ def main():
       roofline['batches_per_launch_sweep'] = {'error': str(e)[:200]}
 
   cpu = None
-  if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == 'ppo' and not args.host_envs:
+  if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == 'ppo'
+      and not args.host_envs):
     cpu = cpu_baseline(args)
 
   # BASELINE configs[2] beside the headline (same command, own process): a short
@@ -1089,7 +1128,7 @@ def main():
   # roofline fractions of its 144 MB gathers and 84 MB write-backs are part of
   # every record.  Never part of `value`.
   workloads = None
-  if (rank == 0 and world == 1 and not use_dist and args.workload == 'ppo' and not args.no_dreamer_leg
+  if (args.full and rank == 0 and world == 1 and not use_dist and args.workload == 'ppo' and not args.no_dreamer_leg
       and not args.host_envs and args.selector == 'uniform' and args.envs == 64
       and args.consec == 1 and args.prefetch == 1):
     del driver, env, stream, policy
@@ -1553,7 +1592,7 @@ def dreamer_leg(args):
   import subprocess
 
   def run(*extra):
-    cmd = [sys.executable, os.path.abspath(__file__), '--workload', 'dreamer', '--no-dreamer-leg',
+    cmd = [sys.executable, os.path.abspath(__file__), '--full', '--workload', 'dreamer', '--no-dreamer-leg',
            '--steps', str(args.dreamer_leg_steps), '--warmup', '200', '--sustained-seconds', '3',
            '--no-cpu-baseline', '--no-context', *extra]
     began = time.perf_counter()
@@ -1587,6 +1626,50 @@ def dreamer_leg(args):
   full['latents_sampled'] = 'all L steps (the reference\'s Replay.sample)'
   leg['full_gather'] = full
   return leg
+
+
+DUMP_BYTES = 64 * 10**6        # --dump-outputs: all files together
+DUMP_MAX_ELEMENTS = 1 << 22    # larger arrays are written as a seeded sample of this many elements
+
+
+def dump_outputs(folder, policy_batch, last_train):
+  """What the timed path computed in its last step, as `folder/<name>.npy`: the
+  policy batch of the last env step and the batch and returns of the last train
+  step.  Floats of up to 32 bits and small integers are written as float32,
+  wider ones as float64.  An array with more than DUMP_MAX_ELEMENTS elements (the
+  sampled images) is written as the elements at a fixed, seeded set of flat
+  indices (`<name>.sample.npy`, sorted indices, the same for every run of the
+  same shape); the smallest arrays go first, and all files together stay within
+  DUMP_BYTES."""
+  arrays = {}
+  if policy_batch is not None:
+    arrays['policy_batch'] = policy_batch
+  for key, value in (last_train.get('batch') or {}).items():
+    if isinstance(value, torch.Tensor):
+      arrays['batch_' + key.replace('/', '_')] = value
+  for key, value in (last_train.get('returns') or {}).items():
+    arrays['train_' + key] = value
+  if torch.cuda.is_available():
+    torch.cuda.synchronize()        # (every stream: the learner's may be another one)
+  os.makedirs(folder, exist_ok=True)
+  left = DUMP_BYTES
+  order = sorted(arrays, key=lambda k: (arrays[k].numel(), k))
+  for i, name in enumerate(order):
+    t = arrays[name]
+    wide = t.dtype in (torch.float64, torch.int32, torch.int64, torch.uint32, torch.uint64)
+    dtype, size = (torch.float64, 8) if wide else (torch.float32, 4)
+    limit = min(DUMP_MAX_ELEMENTS, left // (len(order) - i) // size)
+    flat = t.detach().reshape(-1)
+    if flat.numel() > limit:
+      rng = np.random.default_rng(flat.numel())
+      idx = np.unique(rng.integers(0, flat.numel(), limit))
+      flat = flat[torch.from_numpy(idx).to(flat.device)]
+      name += '.sample'
+    out = flat.to(dtype).cpu().numpy()
+    if not name.endswith('.sample'):
+      out = out.reshape(tuple(t.shape))
+    np.save(os.path.join(folder, name + '.npy'), out)
+    left -= out.nbytes
 
 
 def plain_copy_reference(replay, rows, device, iters=200):

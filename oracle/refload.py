@@ -22,7 +22,10 @@ SHIMS = pathlib.Path(__file__).parent / 'shims'
 
 
 def available():
-  return (REFERENCE / 'embodied' / 'core' / 'replay.py').exists()
+  try:
+    return (REFERENCE / 'embodied' / 'core' / 'replay.py').exists()
+  except OSError:          # a tree this user may not read is no tree here
+    return False
 
 
 def load():

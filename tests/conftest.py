@@ -35,7 +35,8 @@ def pytest_configure(config):
   config.addinivalue_line(
       'markers', 'gpu: needs a real MI355X (run on the GPU box with -m gpu)')
   config.addinivalue_line(
-      'markers', 'reference: needs /root/reference (build container only)')
+      'markers', 'reference: against the reference\'s own code (afresh where its tree is readable, '
+      'else tests/golden/reference_runs.json)')
 
 
 def load_golden(name):

@@ -40,7 +40,7 @@ def run_bench(*flags, env=None):
 
 
 def test_bench_gpus_2_spawns_two_ranks():
-  rec = run_bench('--gpus', '2', '--steps', '20', '--warmup', '5', '--backend', 'gloo')
+  rec = run_bench('--gpus', '2', '--steps', '20', '--warmup', '5', '--backend', 'gloo', '--full')
   assert rec['n_gpus'] == 2 and rec['rccl_ranks'] == 2 and rec['backend'] == 'gloo'
   assert rec['steps'] == 20 and rec['warmup'] == 5
   assert rec['config']['global_envs'] == 2 * rec['config']['envs_per_gpu']
@@ -60,7 +60,7 @@ def test_bench_gpus_2_native_exchange_between_two_real_ranks():
   lib = fake_rccl()
   rec = run_bench('--gpus', '2', '--steps', '40', '--warmup', '5', '--capacity', '20000',
                   '--grad-numel', '100000', '--sustained-seconds', '1', '--prewarm-train-steps', '20',
-                  '--backend', 'gloo', '--comm', 'native', env={'EMB_RCCL_LIB': lib})
+                  '--backend', 'gloo', '--comm', 'native', '--full', env={'EMB_RCCL_LIB': lib})
   assert rec['n_gpus'] == 2 and rec['backend'] == 'gloo'
   native = rec['native_comm']
   assert native['status'] == 'ok' and native['ranks'] == 2 and all(native['checks'].values()), native
@@ -81,7 +81,7 @@ def test_bench_gpus_2_direct_schedule_between_two_real_ranks():
   lib = fake_rccl()
   rec = run_bench('--gpus', '2', '--steps', '40', '--warmup', '5', '--capacity', '20000',
                   '--grad-numel', '100000', '--sustained-seconds', '1', '--prewarm-train-steps', '20',
-                  '--backend', 'gloo', '--comm', 'direct', env={'EMB_RCCL_LIB': lib})
+                  '--backend', 'gloo', '--comm', 'direct', '--full', env={'EMB_RCCL_LIB': lib})
   native = rec['native_comm']
   direct = native['direct']
   assert direct['status'] == 'ok' and all(direct['checks'].values()) and direct['timed_out'] is False, direct
@@ -128,7 +128,7 @@ def test_bench_auto_degrades_when_a_transport_fails_on_one_rank(fault, left):
   what is left, the line is valid and the exit code 0."""
   rec = run_bench('--gpus', '2', '--steps', '40', '--warmup', '5', '--capacity', '20000',
                   '--grad-numel', '100000', '--sustained-seconds', '1', '--prewarm-train-steps', '20',
-                  '--backend', 'gloo', env={'EMB_RCCL_LIB': fake_rccl(), 'EMB_BENCH_FAULT': fault})
+                  '--backend', 'gloo', '--full', env={'EMB_RCCL_LIB': fake_rccl(), 'EMB_BENCH_FAULT': fault})
   native = rec['native_comm']
   broken = native['direct'] if fault.startswith('direct') else native
   assert broken['status'] != 'ok', broken
@@ -162,7 +162,8 @@ def test_bench_all_gather_forms_run_on_the_librarys_transports(comm, exchange):
   train step (emb_direct_exchange_gather / emb_comm_exchange_gather)."""
   rec = run_bench('--gpus', '2', '--steps', '40', '--warmup', '5', '--capacity', '20000',
                   '--grad-numel', '100000', '--sustained-seconds', '1', '--prewarm-train-steps', '20',
-                  '--backend', 'gloo', '--comm', comm, '--exchange', exchange, env={'EMB_RCCL_LIB': fake_rccl()})
+                  '--backend', 'gloo', '--comm', comm, '--exchange', exchange, '--full',
+                  env={'EMB_RCCL_LIB': fake_rccl()})
   native = rec['native_comm']
   assert native['timed_path'] == comm and rec['transports']['exchange'] == exchange
   step = native['per_train_step']
@@ -178,7 +179,8 @@ def test_bench_gpus_8_control_flow():
   agree on their exchange schedule at every fence and rank 0 prints one line
   (gloo: the eight ranks share the test box's one GPU)."""
   rec = run_bench('--gpus', '8', '--steps', '20', '--warmup', '5', '--capacity', '6000',
-                  '--grad-numel', '100000', '--sustained-seconds', '1', '--prewarm-train-steps', '10', '--backend', 'gloo')
+                  '--grad-numel', '100000', '--sustained-seconds', '1', '--prewarm-train-steps', '10', '--backend', 'gloo',
+                  '--full')
   assert rec['n_gpus'] == 8 and rec['rccl_ranks'] == 8 and rec['backend'] == 'gloo'
   assert rec['config']['global_envs'] == 8 * rec['config']['envs_per_gpu']
   assert rec['scaling'] == 'weak' and rec['value'] > 0 and rec['train_steps_per_s'] > 0
@@ -199,7 +201,7 @@ def test_bench_gpus_8_rehearsal_on_one_gpu():
   kernels wait for the GPU, and ONE such all-reduce takes ~100 ms (profiles/
   r06_rehearsal_gpus8_one_gpu.json holds a run with the default size).  The gradient here
   is 400 KB; its dtype is the default f32."""
-  rec = run_bench('--gpus', '8', '--backend', 'gloo', '--no-cpu-baseline', '--steps', '800', '--warmup', '50',
+  rec = run_bench('--gpus', '8', '--backend', 'gloo', '--full', '--no-cpu-baseline', '--steps', '800', '--warmup', '50',
                   '--sustained-seconds', '1', '--grad-numel', '100000', '--capacity', '20000', '--prewarm-train-steps', '20',
                   env={'EMB_RCCL_LIB': fake_rccl()})
   assert rec['n_gpus'] == 8 and rec['rccl_ranks'] == 8 and rec['backend'] == 'gloo'
@@ -222,7 +224,7 @@ def test_bench_gpus_8_rehearsal_on_one_gpu():
   # Eight processes time-sharing the one GPU (collectives off) deliver a fraction of what one
   # process does alone on it -- context switches between their queues -- so the rates are held
   # against each other with wide bounds only: the rehearsal checks agreement of the PROGRAM.
-  single = run_bench('--no-cpu-baseline', '--no-context', '--no-dreamer-leg', '--sustained-seconds', '1',
+  single = run_bench('--full', '--no-cpu-baseline', '--no-context', '--no-dreamer-leg', '--sustained-seconds', '1',
                      '--steps', '800', '--warmup', '50', '--capacity', '20000')
   assert single['metric'] == rec['metric'] and single['unit'] == rec['unit']
   assert single['config']['workload'] == rec['config']['workload']
@@ -270,9 +272,9 @@ def test_bench_comm_c10d_keeps_torch_distributed_in_the_timed_path():
 
 
 def test_bench_short_run_keeps_its_shape():
-  """The driver's short form on one GPU: the line carries roofline, the
+  """The driver's short form on one GPU with --full: the line carries roofline, the
   sustained window and the CPU baseline; the headline region is exactly --steps."""
-  rec = run_bench('--steps', '20', '--warmup', '5', '--cpu-seconds', '2', '--sustained-seconds', '2')
+  rec = run_bench('--full', '--steps', '20', '--warmup', '5', '--cpu-seconds', '2', '--sustained-seconds', '2')
   assert rec['n_gpus'] == 1 and rec['steps'] == 20
   roof = rec['roofline']
   assert roof['bound'] == 'hbm' and roof['unit'] == 'GB/s' and 0 < roof['frac'] < 1
@@ -288,10 +290,10 @@ def test_bench_short_run_keeps_its_shape():
 
 
 def test_default_single_gpu_run_appends_the_dreamer_workload():
-  """BASELINE configs[2] rides in the driver's own command: the PPO line carries
+  """BASELINE configs[2] rides in the driver's own command with --full: the PPO line carries
   `workloads.dreamer` with the rates and the gather / write-back roofline figures
   of a short DreamerV3-shaped run (1M-step uniform replay, latents written back)."""
-  rec = run_bench('--steps', '20', '--warmup', '5', '--sustained-seconds', '0', '--no-cpu-baseline',
+  rec = run_bench('--full', '--steps', '20', '--warmup', '5', '--sustained-seconds', '0', '--no-cpu-baseline',
                   '--no-context', '--dreamer-leg-steps', '400')
   assert rec['config']['workload'].startswith('ppo_atari_pong_64env')     # metric / value unchanged
   assert 'span_move_kernel' in rec['roofline']['kernel'] or 'flat_move_kernel' in rec['roofline']['kernel']
@@ -311,9 +313,9 @@ def test_default_single_gpu_run_appends_the_dreamer_workload():
 
 
 def test_short_form_value_is_the_median_of_sixteen_regions():
-  """`--steps 20` (the driver's form): sixteen fenced regions of exactly 20 steps,
-  `value` = the median one; every region's time is in the line."""
-  rec = run_bench('--steps', '20', '--warmup', '5', '--sustained-seconds', '0', '--no-cpu-baseline',
+  """`--steps 20 --full`: sixteen fenced regions of exactly 20 steps, `value` =
+  the median one; every region's time is in the line."""
+  rec = run_bench('--full', '--steps', '20', '--warmup', '5', '--sustained-seconds', '0', '--no-cpu-baseline',
                   '--no-context', '--no-dreamer-leg')
   regions = rec['regions']
   assert regions['n'] == 16 and len(regions['ms']) == 16 and len(regions['train_steps']) == 16
@@ -323,9 +325,35 @@ def test_short_form_value_is_the_median_of_sixteen_regions():
   rates = regions['env_steps_per_s']
   assert rates['min'] <= rates['median'] <= rates['max'] and rates['median'] == rec['value']
   assert abs(rec['value'] - 20 * 64 / (ms[7] * 1e-3)) / rec['value'] < 1e-3
-  long = run_bench('--steps', '300', '--warmup', '5', '--sustained-seconds', '0', '--no-cpu-baseline',
+  long = run_bench('--full', '--steps', '300', '--warmup', '5', '--sustained-seconds', '0', '--no-cpu-baseline',
                    '--no-context', '--no-dreamer-leg')
   assert long['regions']['n'] == 1
+
+
+def test_plain_run_times_exactly_its_steps_and_dumps_the_same_outputs(tmp_path):
+  """Without --full: one fenced region of exactly --steps steps, nothing measured
+  after it, and --dump-outputs writes the last step's outputs -- the same ones in
+  two runs with the same arguments (seeded inputs)."""
+  import numpy as np
+  dumps = []
+  for run in range(2):
+    out = tmp_path / f'run{run}'
+    rec = run_bench('--steps', '300', '--warmup', '20', '--capacity', '20000', '--dump-outputs', str(out))
+    assert rec['steps'] == 300 and rec['regions']['n'] == 1 and rec['ms_per_step'] > 0
+    # (ms_per_step is rounded to 1e-5 ms, the region's time to 1e-4 ms)
+    assert abs(rec['ms_per_step'] * 300 - rec['regions']['ms'][0]) <= 300 * 0.5e-5 + 0.5e-4 + 1e-9
+    assert rec['sustained'] is None and rec['cpu_baseline'] is None
+    assert 'workloads' not in rec and 'fresh_batches' not in rec and 'other_env_actions' not in rec
+    assert 'batches_per_launch_sweep' not in (rec['roofline'] or {})
+    files = sorted(p.name for p in out.iterdir())
+    assert {'policy_batch.npy', 'batch_reward.npy', 'batch_image.sample.npy',
+            'train_advantage.npy', 'train_target.npy'} <= set(files), files
+    assert sum((out / f).stat().st_size for f in files) <= 64 * 10**6
+    dumps.append({f: np.load(out / f) for f in files})
+  assert dumps[0].keys() == dumps[1].keys()
+  for name, got in dumps[0].items():
+    assert got.dtype in (np.float32, np.float64), name
+    assert np.array_equal(got, dumps[1][name]), name
 
 
 def test_bench_refuses_more_rccl_ranks_than_gpus():

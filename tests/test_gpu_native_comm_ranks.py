@@ -170,7 +170,7 @@ def test_bench_two_ranks_on_real_rccl():
   library's own RCCL exchange in the timed path after its self-check against
   torch.distributed passed on both ranks."""
   from tests.test_gpu_bench_launcher import run_bench
-  rec = run_bench('--gpus', '2', '--steps', '20', '--warmup', '5')
+  rec = run_bench('--gpus', '2', '--steps', '20', '--warmup', '5', '--full')
   assert rec['n_gpus'] == 2 and rec['rccl_ranks'] == 2 and rec['backend'] == 'nccl'
   native = rec['native_comm']
   assert native['status'] == 'ok' and native['ranks'] == 2 and all(native['checks'].values()), native

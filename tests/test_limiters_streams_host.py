@@ -6,6 +6,7 @@ import pytest
 
 from embodied_amd import limiters, streams
 from oracle import np_oracle, refload
+from tests import reference_record
 
 
 def drive(lim):
@@ -34,12 +35,17 @@ def test_samples_per_insert_limiter():
   assert (other.avail, other.size) == (lim.avail, lim.size)
 
 
+@reference_record.recorded('limiter')
+def _reference_limiter():
+  return drive(refload.load().limiters.SamplesPerInsert(2, 4, 3))
+
+
 @pytest.mark.reference
 def test_limiter_matches_reference():
-  if not refload.available():
-    pytest.skip('no /root/reference here')
-  ref = refload.load().limiters.SamplesPerInsert(2, 4, 3)
-  assert drive(ref) == drive(limiters.SamplesPerInsert(2, 4, 3))
+  """The same drive through the reference's SamplesPerInsert (afresh where its
+  tree is readable, recorded elsewhere)."""
+  want = reference_record.check('limiter')
+  assert reference_record.plain(drive(limiters.SamplesPerInsert(2, 4, 3))) == want
 
 
 def test_wait_returns_when_predicate_turns_true():
@@ -197,37 +203,45 @@ class _Numbered:
     self.k = k
 
 
+def _zip_and_map(ns):
+  zipped = iter(ns.Zip([_Numbered(10), _Numbered(20, rows=3)]))
+  mapped = iter(ns.Map(_Numbered(30), lambda batch, k, scale=1: {'x': batch['x'] * scale + k}, 5, scale=2))
+  out = [next(zipped) for _ in range(3)]
+  state = zipped.save()
+  out += [next(zipped) for _ in range(2)]
+  zipped.load(state)
+  out.append(next(zipped))
+  out += [next(mapped), next(mapped)]
+  held = mapped.save()
+  next(mapped)
+  mapped.load(held)
+  out.append(next(mapped))
+  return out, state, held
+
+
+@reference_record.recorded('zip_and_map')
+def _reference_zip_and_map():
+  import importlib
+  refload.load()
+  want, wstate, wheld = _zip_and_map(importlib.import_module('embodied.core.streams'))
+  return {'x': [b['x'] for b in want], 'state': wstate, 'held': wheld}
+
+
 def test_zip_and_map_against_the_reference_classes():
   """streams.py:153-201.  Zip concatenates one batch per source leaf by leaf;
-  Map applies a function; both checkpoint through their sources.  Build
-  container: the same sequence through the reference's own classes."""
-  def build(ns):
-    zipped = iter(ns.Zip([_Numbered(10), _Numbered(20, rows=3)]))
-    mapped = iter(ns.Map(_Numbered(30), lambda batch, k, scale=1: {'x': batch['x'] * scale + k}, 5, scale=2))
-    out = [next(zipped) for _ in range(3)]
-    state = zipped.save()
-    out += [next(zipped) for _ in range(2)]
-    zipped.load(state)
-    out.append(next(zipped))
-    out += [next(mapped), next(mapped)]
-    held = mapped.save()
-    next(mapped)
-    mapped.load(held)
-    out.append(next(mapped))
-    return out, state, held
-
-  got, state, held = build(streams)
+  Map applies a function; both checkpoint through their sources.  The same
+  sequence through the reference's own classes (afresh where its tree is
+  readable, recorded elsewhere)."""
+  got, state, held = _zip_and_map(streams)
   assert state == [3, 3] and held == 2
   assert got[0]['x'].tolist() == [[1, 10]] * 2 + [[1, 20]] * 3 and got[0]['nest']['y'].tolist() == [1] * 5
   assert got[5]['x'][0].tolist() == [4, 10]                       # after load: the 4th batch again
   assert got[6]['x'].tolist() == [[7, 65]] * 2 and got[8]['x'][0].tolist() == [11, 65]
-  if refload.available():
-    ref = refload.load()
-    import importlib
-    want, wstate, wheld = build(importlib.import_module('embodied.core.streams'))
-    assert wstate == state and wheld == held
-    for a, b in zip(got, want):
-      assert (a['x'] == b['x']).all()
+  want = reference_record.check('zip_and_map')
+  assert want['state'] == reference_record.plain(state) and want['held'] == held
+  assert len(want['x']) == len(got)
+  for a, b in zip(got, want['x']):
+    assert (a['x'] == np.array(b)).all()
   # torch batches are concatenated as tensors
   import torch
   class _Tensors(_Numbered):
@@ -239,11 +253,14 @@ def test_zip_and_map_against_the_reference_classes():
     streams.Zip([_Numbered(1)])
 
 
+MIXER_WEIGHTS = {'b': 3.0, 'a': 1.0}
+
+
 def test_mixer_draws_sources_by_weight_and_restores():
   """streams.py:204-243 (cannot run upstream: see the class docstring): the
   source of step s is `default_rng([seed, s]).choice(p=weights / sum)` over the
   sorted keys; save / load restore the step and every source."""
-  weights = {'b': 3.0, 'a': 1.0}
+  weights = dict(MIXER_WEIGHTS)
   mixer = streams.Mixer({'a': _Numbered(1), 'b': _Numbered(2)}, weights, seed=7)
   tags = [int(next(mixer)['x'][0, 1]) for _ in range(200)]
   want = [1 + int(np.random.default_rng(seed=[7, s]).choice(2, p=np.array([0.25, 0.75], np.float32)))
@@ -256,24 +273,28 @@ def test_mixer_draws_sources_by_weight_and_restores():
   assert [next(mixer)['x'][0].tolist() for _ in range(5)] == ahead
   with pytest.raises(ValueError):
     streams.Mixer({'a': _Numbered(1)}, {'b': 1.0})
-  if refload.available():
-    # Build container: the reference's own Mixer with ONE token of `__next__`
-    # repaired (`np.ranodm` -> `np.random`, from its source at run time) and the
-    # `started` flag it asserts on but never sets switched on: the same sources
-    # in the same order.
-    import importlib
-    import inspect
-    import textwrap
-    refload.load()
-    ref_streams = importlib.import_module('embodied.core.streams')
-    source = textwrap.dedent(inspect.getsource(ref_streams.Mixer.__next__))
-    assert source.count('np.ranodm') == 1
-    scope = {}
-    exec(source.replace('np.ranodm', 'np.random'), {'np': np}, scope)
-    Repaired = type('RepairedMixer', (ref_streams.Mixer,), {'__next__': scope['__next__']})
-    theirs = Repaired({'a': _Numbered(1), 'b': _Numbered(2)}, dict(weights), seed=7)
-    theirs.started = True
-    assert [int(next(theirs)['x'][0, 1]) for _ in range(200)] == tags
+  # the reference's own Mixer (afresh where its tree is readable, recorded elsewhere)
+  assert reference_record.check('mixer') == tags
+
+
+@reference_record.recorded('mixer')
+def _reference_mixer():
+  """The reference's own Mixer with ONE token of `__next__` repaired (`np.ranodm`
+  -> `np.random`, from its source at run time) and the `started` flag it asserts
+  on but never sets switched on: the sources it draws, in order."""
+  import importlib
+  import inspect
+  import textwrap
+  refload.load()
+  ref_streams = importlib.import_module('embodied.core.streams')
+  source = textwrap.dedent(inspect.getsource(ref_streams.Mixer.__next__))
+  assert source.count('np.ranodm') == 1
+  scope = {}
+  exec(source.replace('np.ranodm', 'np.random'), {'np': np}, scope)
+  Repaired = type('RepairedMixer', (ref_streams.Mixer,), {'__next__': scope['__next__']})
+  theirs = Repaired({'a': _Numbered(1), 'b': _Numbered(2)}, dict(MIXER_WEIGHTS), seed=7)
+  theirs.started = True
+  return [int(next(theirs)['x'][0, 1]) for _ in range(200)]
 
 
 class _LendingReplay:

@@ -13,6 +13,7 @@ import torch
 
 from oracle import gen_normalize_golden as gen
 from oracle import np_oracle
+from tests import reference_record
 
 GOLDEN = pathlib.Path(__file__).parent / 'golden' / 'normalize.npz'
 # float32 running statistics over 40 steps: the tolerance BASELINE.json's
@@ -53,16 +54,12 @@ def test_product_normalize_matches_the_reference_class(case):
   np.testing.assert_allclose(np.stack(rows), want, rtol=RTOL, atol=ATOL)
 
 
-@pytest.mark.reference
-def test_normalize_fixture_is_current():
-  """Build container only: the committed fixture equals a fresh execution of the
-  reference's class."""
-  from oracle import refload
-  if not refload.available():
-    pytest.skip('no /root/reference here')
+@reference_record.recorded('normalize')
+def _reference_normalize():
+  """A fresh execution of the reference's class: its source lines and a digest
+  of every case's rows."""
   Normalize, lines = gen.reference_class()
-  want = golden()
-  assert tuple(want['lines']) == lines
+  out = {'lines': list(lines)}
   for case, (impl, fields) in enumerate(gen.CASES):
     norm = Normalize(impl)
     for name, value in fields.items():
@@ -70,4 +67,16 @@ def test_normalize_fixture_is_current():
     rows = [np.array(norm.stats(), np.float64)]
     for step in range(gen.STEPS):
       rows.append(np.array(norm(gen.inputs(case, step), True), np.float64))
-    assert np.array_equal(np.stack(rows), want[f'case{case}']), case
+    out[f'case{case}'] = reference_record.digest({'rows': np.stack(rows)})
+  return out
+
+
+@pytest.mark.reference
+def test_normalize_fixture_is_current():
+  """The committed fixture equals an execution of the reference's class (afresh
+  where the reference tree is readable, its recorded digests elsewhere)."""
+  ref = reference_record.check('normalize')
+  want = golden()
+  assert reference_record.plain(tuple(want['lines'])) == ref['lines']
+  for case in range(len(gen.CASES)):
+    assert reference_record.digest({'rows': want[f'case{case}']}) == ref[f'case{case}'], case

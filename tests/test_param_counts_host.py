@@ -1,7 +1,7 @@
 """The gradient size the multi-GPU bench all-reduces by default is the shipped PPO
 model's parameter total, counted module by module (tools/count_params.py) -- not
-an estimate.  The count is checked against a hand-derived breakdown and, in the
-build container, against the reference's own yaml."""
+an estimate.  The count is checked against a hand-derived breakdown and against
+the reference's own yaml (tests/reference_record.py)."""
 import os
 import pathlib
 import re
@@ -9,6 +9,8 @@ import sys
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / 'tools'))
+
+from tests import reference_record  # noqa: E402
 
 
 def test_ppo_parameter_total_is_the_default_gradient_size():
@@ -30,11 +32,23 @@ def test_ppo_parameter_total_is_the_default_gradient_size():
   assert re.search(r"--grad-dtype', default='f32'", bench)          # the reference's precision (jax/opt.py:52-54)
 
 
-def test_counts_follow_the_reference_yaml_when_it_is_there():
+@reference_record.recorded('param_count_configs')
+def _reference_configs():
+  """The two `defaults.agent` blocks of the reference's yaml files, reduced to the
+  fields counted here."""
   import count_params as cp
-  ppo_cfg, dreamer_cfg = cp.from_reference('/root/reference')
-  if ppo_cfg is None:            # (GPU box: no reference tree)
-    return
-  assert ppo_cfg == cp.PPO_AGENT and dreamer_cfg == cp.DREAMER_AGENT
-  crafter = sum(cp.dreamer(dreamer_cfg, (64, 64, 3), 0, 17).values())
+  from oracle import refload
+  ppo_cfg, dreamer_cfg = cp.from_reference(str(refload.REFERENCE))
+  assert ppo_cfg is not None, 'the reference yaml files could not be read'
+  return {'ppo': ppo_cfg, 'dreamer': dreamer_cfg}
+
+
+def test_counts_follow_the_reference_yaml_when_it_is_there():
+  """The counted configurations are the reference's yaml defaults (read afresh
+  where the reference tree is readable, recorded elsewhere)."""
+  import count_params as cp
+  want = reference_record.check('param_count_configs')
+  assert reference_record.plain(cp.PPO_AGENT) == want['ppo']
+  assert reference_record.plain(cp.DREAMER_AGENT) == want['dreamer']
+  crafter = sum(cp.dreamer(cp.DREAMER_AGENT, (64, 64, 3), 0, 17).values())
   assert 150e6 < crafter < 200e6          # "size200m" (dreamerv3/configs.yaml:146-149)

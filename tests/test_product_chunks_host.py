@@ -11,6 +11,7 @@ import pathlib
 import numpy as np
 import pytest
 
+from tests import reference_record
 from tools import write_product_chunks as scenario
 
 FIXTURE = pathlib.Path(__file__).parent / 'golden' / 'product_chunks'
@@ -28,6 +29,15 @@ def files():
   names = sorted(p.name for p in FIXTURE.glob('*.npz'))
   assert names, 'tests/golden/product_chunks is empty'
   return names
+
+
+def fixture_digest():
+  """One digest over every chunk file of the fixture: its name and its arrays."""
+  digests = {}
+  for name in files():
+    with np.load(FIXTURE / name) as f:
+      digests[name] = reference_record.digest({k: f[k] for k in f.files})
+  return reference_record.digest({name: np.frombuffer(d.encode(), np.uint8) for name, d in digests.items()})
 
 
 def expected_windows():
@@ -71,48 +81,65 @@ def test_file_names_and_arrays_follow_the_chunk_format():
       assert a[1] == b[0], (worker, a, b)
 
 
-@pytest.mark.reference
-def test_reference_loads_the_products_chunk_files(tmp_path):
-  """Build container only: the real reference Replay restores from the
-  product-written directory exactly the windows that were inserted, goes on
-  adding to it, and saves / reloads the mix."""
-  from oracle import refload
-  if not refload.available():
-    pytest.skip('no /root/reference here')
+@reference_record.recorded('reference_loads_product_chunks')
+def _reference_loads_product_chunks():
+  """What the real reference Replay observes when it restores from a copy of the
+  product-written directory, samples and writes back through its own path, goes
+  on adding to it, and saves / reloads the mix."""
   import shutil
+  import tempfile
+  from oracle import refload
   ref = refload.load()
-  work = tmp_path / 'replay'
-  shutil.copytree(FIXTURE, work)
   L = scenario.LENGTH
-  reader = ref.replay.Replay(L, capacity=None, directory=str(work), chunksize=scenario.CHUNKSIZE,
-                             save_wait=True)
-  reader.load()
+  with tempfile.TemporaryDirectory() as tmp:
+    work = pathlib.Path(tmp) / 'replay'
+    shutil.copytree(FIXTURE, work)
+    reader = ref.replay.Replay(L, capacity=None, directory=str(work), chunksize=scenario.CHUNKSIZE,
+                               save_wait=True)
+    reader.load()
+    loaded = len(reader)
+    windows, rows_match = [], True
+    for itemid in sorted(reader.items):
+      chunkid, index = reader.items[itemid]
+      seq = reader._getseq(chunkid, index, concat=True)
+      windows.append(list(zip(seq['worker'].tolist(), seq['step'].tolist())))
+      for i in range(L):
+        ref_step = scenario.step_of(int(seq['worker'][i]), int(seq['step'][i]))
+        rows_match &= bool((seq['vec'][i] == ref_step['vec']).all() and (seq['image'][i] == ref_step['image']).all())
+    # sampling through the reference's own path, with its annotations
+    batch = reader.sample(8)
+    shapes = {'image': list(batch['image'].shape), 'stepid': list(batch['stepid'].shape)}
+    # write-back by step id lands on the loaded rows (replay.py:152-165, 241-263)
+    reader.update({'stepid': batch['stepid'], 'vec': np.full_like(batch['vec'], -1.0)})
+    again = reader.sample(64)
+    hit = {bytes(s) for s in batch['stepid'].reshape(-1, 20)}
+    written_back = all(bool((vec == -1.0).all())
+                       for sid, vec in zip(again['stepid'].reshape(-1, 20), again['vec'].reshape(-1, 3))
+                       if bytes(sid) in hit)
+    # the reference continues the run: new steps, new chunk files beside the product's
+    for t in range(scenario.STEPS, scenario.STEPS + 6):
+      for w in range(scenario.WORKERS):
+        reader.add({k: v for k, v in scenario.step_of(w, t).items()}, worker=w)
+    reader.save()
+    fresh = ref.replay.Replay(L, capacity=None, directory=str(work), chunksize=scenario.CHUNKSIZE)
+    fresh.load()
+    return {'fixture': fixture_digest(), 'loaded': loaded, 'windows': sorted(windows), 'rows_match': rows_match, 'sample_shapes': shapes,
+            'written_back': written_back, 'reloaded': len(fresh)}
+
+
+@pytest.mark.reference
+def test_reference_loads_the_products_chunk_files():
+  """The real reference Replay restores from the product-written directory
+  exactly the windows that were inserted, goes on adding to it, and saves /
+  reloads the mix (afresh where the reference tree is readable, its recorded
+  observations elsewhere)."""
+  ref = reference_record.check('reference_loads_product_chunks')
+  assert ref['fixture'] == fixture_digest(), 'tests/golden/product_chunks changed since the record was made'
   want = expected_windows()
-  assert len(reader) == len(want)
-  got = set()
-  for itemid in sorted(reader.items):
-    chunkid, index = reader.items[itemid]
-    seq = reader._getseq(chunkid, index, concat=True)
-    got.add(tuple(zip(seq['worker'].tolist(), seq['step'].tolist())))
-    for i in range(L):
-      ref_step = scenario.step_of(int(seq['worker'][i]), int(seq['step'][i]))
-      assert (seq['vec'][i] == ref_step['vec']).all() and (seq['image'][i] == ref_step['image']).all()
-  assert got == want
-  # sampling through the reference's own path, with its annotations
-  batch = reader.sample(8)
-  assert batch['image'].shape == (8, L, 2, 2, 3) and batch['stepid'].shape == (8, L, 20)
-  # write-back by step id lands on the loaded rows (replay.py:152-165, 241-263)
-  reader.update({'stepid': batch['stepid'], 'vec': np.full_like(batch['vec'], -1.0)})
-  again = reader.sample(64)
-  hit = {bytes(s) for s in batch['stepid'].reshape(-1, 20)}
-  for sid, vec in zip(again['stepid'].reshape(-1, 20), again['vec'].reshape(-1, 3)):
-    if bytes(sid) in hit:
-      assert (vec == -1.0).all()
-  # the reference continues the run: new steps, new chunk files beside the product's
-  for t in range(scenario.STEPS, scenario.STEPS + 6):
-    for w in range(scenario.WORKERS):
-      reader.add({k: v for k, v in scenario.step_of(w, t).items()}, worker=w)
-  reader.save()
-  fresh = ref.replay.Replay(L, capacity=None, directory=str(work), chunksize=scenario.CHUNKSIZE)
-  fresh.load()
-  assert len(fresh) == len(want) + scenario.WORKERS * (6 - L + 1)
+  L = scenario.LENGTH
+  assert ref['loaded'] == len(want)
+  assert {tuple(map(tuple, w)) for w in ref['windows']} == want
+  assert ref['rows_match']
+  assert ref['sample_shapes'] == {'image': [8, L, 2, 2, 3], 'stepid': [8, L, 20]}
+  assert ref['written_back']
+  assert ref['reloaded'] == len(want) + scenario.WORKERS * (6 - L + 1)

@@ -9,6 +9,7 @@ import numpy as np
 
 import embodied_amd as emb
 from embodied_amd.run.stats import EpisodeStats
+from tests import reference_record
 
 
 class Sink:
@@ -263,45 +264,56 @@ def _reference_logfn(logger, epstats):
   return namespace['logfn']
 
 
-def test_episode_stats_equal_the_references_own_logfn():
-  """Build container only: the vectorised `EpisodeStats` against the reference's
-  `logfn` itself, executed from its source (not a restatement), on random
-  episodes with images, rewards and scalar `log/*` values."""
-  import pytest
-  from oracle import refload
-  if not refload.available():
-    pytest.skip('no /root/reference here')
-  n, steps = 5, 400
+def _random_episodes(n=5, steps=400):
+  """Random episodes with images, rewards and scalar `log/*` values: one batch of
+  `n` envs' transitions per step."""
   gen = np.random.default_rng(1)
+  is_last = np.zeros(n, bool)
+  for t in range(steps):
+    is_first = is_last.copy() if t else np.ones(n, bool)
+    is_last = gen.random(n) < 0.07
+    reward = np.where(gen.random(n) < 0.5, 0.0, gen.standard_normal(n)).astype(np.float32)
+    yield {
+        'reward': reward, 'is_first': is_first, 'is_last': is_last,
+        'image': gen.integers(0, 255, (n, 4, 4, 3), dtype=np.uint8),
+        'log/height': gen.standard_normal(n).astype(np.float32),
+        'log/coins': gen.integers(0, 3, n).astype(np.float32)}
 
+
+@reference_record.recorded('episode_stats')
+def _reference_episode_stats():
+  """The reference's `logfn` on `_random_episodes`: the rows it logged, sorted."""
   class ScalarSink(Sink):
     # the reference keeps worker 0's image stacks in the episode result (its
     # video logging, `policy_*`): not a statistic, not kept
     def add(self, mapping, prefix=None):
       super().add({k: v for k, v in mapping.items() if np.ndim(v) == 0}, prefix)
 
-  ours_log, ours_ep = Sink(), Sink()
   want_log, want_ep = ScalarSink(), ScalarSink()
-  stats = EpisodeStats(ours_log, ours_ep)
   logfn = _reference_logfn(want_log, want_ep)
-  is_last = np.zeros(n, bool)
-  for t in range(steps):
-    is_first = is_last.copy() if t else np.ones(n, bool)
-    is_last = gen.random(n) < 0.07
-    reward = np.where(gen.random(n) < 0.5, 0.0, gen.standard_normal(n)).astype(np.float32)
-    trans = {
-        'reward': reward, 'is_first': is_first, 'is_last': is_last,
-        'image': gen.integers(0, 255, (n, 4, 4, 3), dtype=np.uint8),
-        'log/height': gen.standard_normal(n).astype(np.float32),
-        'log/coins': gen.integers(0, 3, n).astype(np.float32)}
-    stats.on_batch(trans, np.arange(n))
-    for i in range(n):
+  for trans in _random_episodes():
+    for i in range(len(trans['reward'])):
       logfn({k: v[i] for k, v in trans.items()}, i)
-  stats.flush()
-  assert len(want_log.rows) > 20 and len(want_ep.rows) == len(want_log.rows)
   key = lambda row: sorted(row.items())
-  for ours, want in ((ours_log, want_log), (ours_ep, want_ep)):
-    a, b = sorted(map(key, ours.rows)), sorted(map(key, want.rows))
+  return {'log': sorted(map(key, want_log.rows)), 'episode': sorted(map(key, want_ep.rows))}
+
+
+def test_episode_stats_equal_the_references_own_logfn():
+  """The vectorised `EpisodeStats` against the reference's `logfn` itself,
+  executed from its source (not a restatement), on random episodes with images,
+  rewards and scalar `log/*` values -- afresh where the reference tree is
+  readable, its recorded rows elsewhere."""
+  ours_log, ours_ep = Sink(), Sink()
+  stats = EpisodeStats(ours_log, ours_ep)
+  for trans in _random_episodes():
+    stats.on_batch(trans, np.arange(len(trans['reward'])))
+  stats.flush()
+  want = reference_record.check('episode_stats')
+  want_log, want_ep = want['log'], want['episode']
+  assert len(want_log) > 20 and len(want_ep) == len(want_log)
+  key = lambda row: sorted(row.items())
+  for ours, b in ((ours_log, want_log), (ours_ep, want_ep)):
+    a = sorted(map(key, ours.rows))
     assert len(a) == len(b)
     for x, y in zip(a, b):
       assert [k for k, _ in x] == [k for k, _ in y]

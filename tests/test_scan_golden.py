@@ -6,10 +6,13 @@ in the same order).  GPU: the HIP scans are within 1e-5 (north_star's
 float-return tolerance; the kernels use a parallel affine scan with FMA, which
 rounds differently from the sequential loop at ~1e-7 relative).
 """
+import pathlib
+
 import numpy as np
 import pytest
 
 from oracle import np_oracle
+from tests import reference_record
 from tests import scan_cases as cases
 from tests.conftest import GOLDEN
 
@@ -85,22 +88,34 @@ def test_oracle_split_and_abstract_equal_reference_fixture(director, seed, shape
     assert np.array_equal(np_oracle.abstract_traj(x, traj['cont'], k, kind), want), key
 
 
-@pytest.mark.reference
-def test_scan_fixtures_are_current(batch_major, director, tmp_path, monkeypatch):
-  """Build container only: re-running the generator on /root/reference gives
-  the committed fixtures."""
-  from oracle import refload
-  if not refload.available():
-    pytest.skip('no /root/reference here')
+@reference_record.recorded('scan_fixtures')
+def _reference_scan_fixtures():
+  """The generator run on the reference's source, into a scratch tree: a digest per file."""
+  import tempfile
   from oracle import gen_scan_golden as gen
-  monkeypatch.setattr(gen, 'ROOT', tmp_path)
-  (tmp_path / 'tests').mkdir()
-  gen.main()
-  for name, want in (('scan_batch_major', batch_major), ('scan_director', director)):
-    with np.load(tmp_path / 'tests' / 'golden' / f'{name}.npz') as f:
-      assert set(f.files) == set(want)
-      for key in f.files:
-        assert np.array_equal(f[key], want[key]), key
+  root = gen.ROOT
+  with tempfile.TemporaryDirectory() as tmp:
+    gen.ROOT = pathlib.Path(tmp)
+    try:
+      (gen.ROOT / 'tests').mkdir()
+      gen.main()
+      out = {}
+      for name in ('scan_batch_major', 'scan_director'):
+        with np.load(gen.ROOT / 'tests' / 'golden' / f'{name}.npz') as f:
+          out[name] = reference_record.digest({k: f[k] for k in f.files})
+      return out
+    finally:
+      gen.ROOT = root
+
+
+@pytest.mark.reference
+def test_scan_fixtures_are_current(batch_major, director):
+  """Re-running the generator on the reference's source gives the committed
+  fixtures (afresh where the reference tree is readable, its recorded digests
+  elsewhere)."""
+  want = reference_record.check('scan_fixtures')
+  assert reference_record.digest(batch_major) == want['scan_batch_major']
+  assert reference_record.digest(director) == want['scan_director']
 
 
 # ------------------------------------------------------------------ HIP path --

@@ -3,7 +3,7 @@ from the reference's wrappers.py through its own `wrap_env` chain.  CPU only."""
 import numpy as np
 import pytest
 
-from tests import adapters, scenarios
+from tests import adapters, reference_record, scenarios
 from tests.conftest import assert_same, load_golden
 
 
@@ -13,14 +13,17 @@ def test_wrappers_match_reference_golden(name):
   assert_same(got, load_golden(name), name)
 
 
+for _name in scenarios.HOST_SCENARIOS:
+  reference_record.recorded(f'host_golden/{_name}')(
+      lambda name=_name: reference_record.digest(scenarios.HOST_SCENARIOS[name](adapters.reference_ns())))
+
+
 @pytest.mark.reference
 @pytest.mark.parametrize('name', sorted(scenarios.HOST_SCENARIOS))
 def test_host_golden_is_current(name):
-  from oracle import refload
-  if not refload.available():
-    pytest.skip('no /root/reference here')
-  got = scenarios.HOST_SCENARIOS[name](adapters.reference_ns())
-  assert_same(got, load_golden(name), name)
+  """The committed fixtures equal the reference's run (fresh where its tree is
+  readable, its recorded digest elsewhere)."""
+  assert reference_record.digest(load_golden(name)) == reference_record.check(f'host_golden/{name}'), name
 
 
 def test_wrapped_envs_run_under_the_driver():

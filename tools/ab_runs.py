@@ -11,7 +11,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BASE = ['--no-cpu-baseline', '--no-context', '--no-dreamer-leg', '--sustained-seconds', '5']
+BASE = ['--full', '--no-cpu-baseline', '--no-context', '--no-dreamer-leg', '--sustained-seconds', '5']
 
 
 def main():

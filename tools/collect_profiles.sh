@@ -10,23 +10,23 @@ O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 # the headline line, un-profiled (bench.py's default: kernel arguments in host memory)
-python "$R/bench.py" > "$O/bench_default.json" 2>/dev/null
+python "$R/bench.py" --full > "$O/bench_default.json" 2>/dev/null
 # the runtime's default argument placement, for DESIGN.md 4's A/B
-HIP_FORCE_DEV_KERNARG=1 python "$R/bench.py" --no-cpu-baseline --no-dreamer-leg > "$O/bench_device_kernargs.json" 2>/dev/null
-python "$R/bench.py" --workload dreamer --context-only --steps 5000 --sustained-seconds 3 --no-dreamer-leg 2>/dev/null | grep '^{' > "$O/bench_dreamer.json"
-python "$R/bench.py" --workload dreamer --steps 5000 --sustained-seconds 3 --no-dreamer-leg 2>/dev/null | grep '^{' > "$O/bench_dreamer_full_gather.json"
+HIP_FORCE_DEV_KERNARG=1 python "$R/bench.py" --full --no-cpu-baseline --no-dreamer-leg > "$O/bench_device_kernargs.json" 2>/dev/null
+python "$R/bench.py" --full --workload dreamer --context-only --steps 5000 --sustained-seconds 3 --no-dreamer-leg 2>/dev/null | grep '^{' > "$O/bench_dreamer.json"
+python "$R/bench.py" --full --workload dreamer --steps 5000 --sustained-seconds 3 --no-dreamer-leg 2>/dev/null | grep '^{' > "$O/bench_dreamer_full_gather.json"
 # the A/B of the early insert on this box (alternating runs; same everything else)
 # the driver's short form
-python "$R/bench.py" --steps 20 --warmup 5 2>/dev/null | grep '^{' > "$O/bench_steps20.json"
+python "$R/bench.py" --full --steps 20 --warmup 5 2>/dev/null | grep '^{' > "$O/bench_steps20.json"
 # --stats of the SAME default command
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/st -o st -- \
-  python "$R/bench.py" --no-cpu-baseline --no-dreamer-leg --no-context > "$O/bench_under_rocprof.json" 2>"$O/stats_bench.log"
+  python "$R/bench.py" --full --no-cpu-baseline --no-dreamer-leg --no-context > "$O/bench_under_rocprof.json" 2>"$O/stats_bench.log"
 cp /tmp/st/st_kernel_stats.csv "$O/kernel_stats_bench.csv"
 HIP_FORCE_DEV_KERNARG=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/st1 -o st -- \
-  python "$R/bench.py" --no-cpu-baseline --no-dreamer-leg > "$O/bench_device_kernargs_under_rocprof.json" 2>/dev/null
+  python "$R/bench.py" --full --no-cpu-baseline --no-dreamer-leg > "$O/bench_device_kernargs_under_rocprof.json" 2>/dev/null
 cp /tmp/st1/st_kernel_stats.csv "$O/kernel_stats_bench_device_kernargs.csv"
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/st2 -o st -- \
-  python "$R/bench.py" --workload dreamer --context-only --steps 5000 --sustained-seconds 0 --no-cpu-baseline > /dev/null 2>&1
+  python "$R/bench.py" --full --workload dreamer --context-only --steps 5000 --sustained-seconds 0 --no-cpu-baseline > /dev/null 2>&1
 cp /tmp/st2/st_kernel_stats.csv "$O/kernel_stats_dreamer.csv"
 for counter in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $counter --kernel-trace --output-format csv -d /tmp/p_$counter -o p -- \
@@ -54,9 +54,9 @@ HIP_FORCE_DEV_KERNARG=0 rocprofv3 --kernel-trace --output-format csv -d /tmp/up 
   python "$R/tools/bench_update.py" 16 > /dev/null 2>&1
 python "$R/tools/summarize_trace.py" /tmp/up/up_kernel_trace.csv 100 > "$O/update_image_rows.csv" 2>/dev/null || true
 # the multi-rank code path with RCCL as the transport, one rank (what a 1-GPU box can run)
-python "$R/bench.py" --force-dist --no-cpu-baseline --no-context --sustained-seconds 5 2>/dev/null \
+python "$R/bench.py" --full --force-dist --no-cpu-baseline --no-context --sustained-seconds 5 2>/dev/null \
   | grep '^{' > "$O/bench_world1_rccl.json" || true
-python "$R/bench.py" --force-dist --comm c10d --no-cpu-baseline --no-context --sustained-seconds 5 2>/dev/null \
+python "$R/bench.py" --full --force-dist --comm c10d --no-cpu-baseline --no-context --sustained-seconds 5 2>/dev/null \
   | grep '^{' > "$O/bench_world1_rccl_c10d.json" || true
 python - "$O" <<'PY'
 import csv, json, sys

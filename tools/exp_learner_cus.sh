@@ -11,7 +11,7 @@ for i in $(seq 1 $N); do
       s1) F="--streams 1";;
       *) F="--streams 2 --learner-cus ${v#s2_}";;
     esac
-    python "$R/bench.py" --no-cpu-baseline --no-context --no-dreamer-leg --sustained-seconds 4 $F "$@" 2>/dev/null | grep '^{' > "$O/${v}_$i.json"
+    python "$R/bench.py" --full --no-cpu-baseline --no-context --no-dreamer-leg --sustained-seconds 4 $F "$@" 2>/dev/null | grep '^{' > "$O/${v}_$i.json"
     python - "$O/${v}_$i.json" "$v round $i $*" <<'PY'
 import json, sys
 try:
