@@ -159,6 +159,8 @@ SIGNATURES = {
     'emb_replay_sample_grouped': [p, i64, i32, p, i32, i64, p, p, p],
     'emb_replay_sample_heads': [p, i64, i32, p, p, p, p, p],
     'emb_replay_update': [p, i64, i64, p, i32, p, p, p],
+    'emb_replay_update_grouped': [p, i64, i64, p, i32, p, p, i32, i64, p],
+    'emb_replay_bind_owner': [p, i64],
     'emb_replay_gather_rows': [p, p, i64, i64, p, p],
     'emb_replay_scatter_rows': [p, p, i64, i32, p, p, p],
     'emb_replay_profile': [p, i32],

@@ -59,6 +59,11 @@ struct emb_replay {
   std::vector<uint32_t> stamp;                     // update: last-writer-wins marks per pool row
   uint32_t stamp_epoch = 0;
   std::vector<emb::StepId> ids;
+  // Sharded pools (emb_replay_bind_owner): the owner whose slot range this
+  // process holds, -1 = unbound.  A bound handle plans no pool access outside
+  // that range: such windows travel as rows -1.
+  int64_t owner = -1;
+  std::vector<int32_t> owned_rows;                 // gather / scatter rows: the caller's table, foreign windows cut
   // Actor and learner on different HIP streams (StreamOrder below).
   bool multistream = false;
   StreamOrder order;

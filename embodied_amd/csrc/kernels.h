@@ -35,7 +35,7 @@ struct MovePlan {
   //   rows_host   the same table on the host: if it fits it travels in the
   //               kernel arguments (no upload, no dependent global load)
   //   spans_host  per sequence {row0, count0, row1}: windows that cross at most
-  //               one chunk boundary, n_rows = n_seq * seq_len            [gather]
+  //               one chunk boundary, n_rows = n_seq * seq_len  [gather, write-back]
   const int32_t* rows = nullptr;
   const int32_t* rows_host = nullptr;
   const int32_t* spans_host = nullptr;
@@ -43,9 +43,10 @@ struct MovePlan {
   // The process keeps kernel arguments in host memory (HIP_FORCE_DEV_KERNARG=0):
   // prefer the mover with the fewest argument readers.
   bool args_in_host_memory = false;
-  // Gather only: batch side cut into groups of `group` sequences whose starts
-  // are `group_stride` bytes apart (every key.batch is then the key's offset
-  // inside group 0); 0 = dense.
+  // Batch side cut into groups of `group` sequences whose starts are
+  // `group_stride` bytes apart (every key.batch is then the key's offset inside
+  // group 0); 0 = dense.  Gathers and plain scatters (a grouped write-back); a
+  // plan with mask_bits or inline_key is refused.
   int32_t group = 0;
   int64_t group_stride = 0;
   // Scatter only: the batch bytes of this key (4-byte multiple rows, e.g. the

@@ -88,11 +88,12 @@ struct alignas(16) MoveTables {
   int8_t mask_dtype[kMaxKeys];
   uint8_t* mask_out[kMaxKeys];
   const uint8_t* mask_flags;
-  // Gather only: the batch side in groups of `group` sequences, `group_stride`
-  // bytes apart (0 = one dense (n_rows, rowbytes) array per key).  Sequence s of
-  // key k starts at key.batch + (s / group) * group_stride + (s % group) * L *
+  // The batch side in groups of `group` sequences, `group_stride` bytes apart
+  // (0 = one dense (n_rows, rowbytes) array per key).  Sequence s of key k
+  // starts at key.batch + (s / group) * group_stride + (s % group) * L *
   // rowbytes: the layout of a packed batch cut into per-destination-rank blocks
-  // (distributed.py, DP-slice exchange).
+  // (distributed.py, DP-slice exchange), written by a grouped gather and read
+  // by a grouped write-back (emb_replay_update_grouped).
   int32_t group;
   int64_t group_stride;
 };
@@ -489,7 +490,10 @@ __device__ __forceinline__ void scatter_block(const MoveArgs& a, const MoveTable
     gstore<uint32_t>(key.pool + row * key.rowbytes + off, w);
     return;
   }
-  copy_bytes(key.batch + r * key.rowbytes + off, key.pool + row * key.rowbytes + off, unit);
+  // (grouped sources: batch_offset; a write-back moves whole sequences, klen = L)
+  const int64_t src = tb.group == 0 ? r * key.rowbytes
+                                    : batch_offset(tb, key, L, seq, static_cast<uint32_t>(r) - seq * L);
+  copy_bytes(key.batch + src + off, key.pool + row * key.rowbytes + off, unit);
 }
 
 // A flat launch has first_block[n_keys] virtual blocks and exactly that many
@@ -750,8 +754,10 @@ hipError_t prepare_move(const MovePlan& plan, MoveLaunch* out, bool gather) {
   t.group_stride = plan.group_stride;
   h.group = t.group;
   h.group_stride = t.group_stride;
+  // Grouped batch sides: gathers and plain write-backs (not the masked insert,
+  // not inline step ids), 16-byte aligned groups.
   if (t.group && (plan.group_stride % 16 != 0 || plan.mask_bits || plan.inline_key >= 0))
-    return hipErrorInvalidValue;       // gather-side layout only, 16-byte aligned groups
+    return hipErrorInvalidValue;
   t.n_keys = plan.n_keys;
   t.n_rows = plan.n_rows;
   t.seq_len = plan.seq_len < 1 ? 1 : plan.seq_len;

@@ -112,6 +112,56 @@ static void sample_index_locked(emb_replay* rep, int64_t batch, int32_t mode, in
   if (spans && !spans_ok) spans->clear();
 }
 
+// Owner binding (emb_replay_bind_owner): pool rows [lo, hi) of the bound owner's
+// slot range; false while the handle is unbound.
+static bool owner_range(const emb_replay* rep, int64_t* lo, int64_t* hi) {
+  if (rep->owner < 0) return false;
+  const emb::ReplayConfig& c = rep->index->config();
+  const int64_t per = c.n_slots / c.owners * c.chunksize;
+  *lo = rep->owner * per;
+  *hi = *lo + per;
+  return true;
+}
+
+// Windows of seq_len rows that touch a row outside the bound owner's range
+// become rows -1 as a whole (a window is one worker's chunk chain: it never
+// mixes owners).  True if a window was cut.
+static bool cut_foreign(const emb_replay* rep, int32_t* rows, int64_t n_rows, int64_t seq_len) {
+  int64_t lo, hi;
+  if (!owner_range(rep, &lo, &hi)) return false;
+  bool cut = false;
+  for (int64_t s = 0; s + seq_len <= n_rows; s += seq_len) {
+    bool foreign = false;
+    for (int64_t j = 0; j < seq_len && !foreign; ++j)
+      foreign = rows[s + j] >= 0 && (rows[s + j] < lo || rows[s + j] >= hi);
+    if (foreign) {
+      std::fill(rows + s, rows + s + seq_len, -1);
+      cut = true;
+    }
+  }
+  return cut;
+}
+
+// A caller's row table as a bound handle may move it: the table itself, or a
+// copy with its foreign windows cut.
+static const int32_t* owned_table(emb_replay* rep, const int32_t* rows, int64_t n_rows, int64_t seq_len) {
+  int64_t lo, hi;
+  if (!owner_range(rep, &lo, &hi)) return rows;
+  bool any = false;
+  for (int64_t i = 0; i < n_rows && !any; ++i) any = rows[i] >= 0 && (rows[i] < lo || rows[i] >= hi);
+  if (!any) return rows;
+  rep->owned_rows.assign(rows, rows + n_rows);
+  cut_foreign(rep, rep->owned_rows.data(), n_rows, seq_len);
+  return rep->owned_rows.data();
+}
+
+int32_t emb_replay_bind_owner(emb_replay_t* rep, int64_t owner) {
+  REP_OP({
+    need(owner >= -1 && owner < rep->index->config().owners, "bind_owner: owner out of range");
+    rep->owner = owner;
+  });
+}
+
 int32_t emb_replay_add_index(emb_replay_t* rep, int64_t n, const int64_t* workers,
                              int32_t* rows_out, uint8_t* stepids_out, int32_t* new_chunks_out) {
   REP_OP({
@@ -721,6 +771,7 @@ static void sample_locked(emb_replay* rep, int64_t batch, int32_t mode, void* co
   HostLap hp;
   rep->rows.resize(batch * L);
   sample_index_locked(rep, batch, mode, rep->rows.data(), online_out, &rep->spans, first_stepids_out);
+  if (cut_foreign(rep, rep->rows.data(), batch * L, L)) rep->spans.clear();   // (the span mover has no skip)
   if (rep->carry.active) {
     // A carried publish holds the NEWEST step of every worker stream: a sampled
     // window reads one of its rows only as its own last row.  Settle the carry
@@ -769,69 +820,85 @@ static KeyList list_subset(emb_replay* rep, int32_t n_keys, const int32_t* key_i
   return list;
 }
 
+static void update_locked(emb_replay* rep, int64_t B, int64_t T, const uint8_t* stepids,
+                          int32_t n_keys, const int32_t* key_ids, const void* const* src,
+                          int32_t group, int64_t group_stride, hipStream_t stream) {
+  need(B >= 0 && T >= 1 && stepids, "update: bad arguments");
+  need(group >= 0 && group_stride >= 0 && (group == 0 || group_stride % 16 == 0),
+       "update: bad source groups");
+  settle_carry(rep);
+  if (B == 0) return;
+  KeyList list = list_subset(rep, n_keys, key_ids, src);
+  list.seq_len = static_cast<int32_t>(T);
+  list.group = group;
+  list.group_stride = group_stride;
+  rep->rows.resize(B * T);
+  rep->spans.resize(3 * B);
+  bool compact = true;    // every window resolved into at most two runs of pool rows
+  for (int64_t i = 0; i < B; ++i) {
+    emb::ReplayIndex::Pos pos;
+    if (rep->index->parse_stepid(stepids + i * EMB_STEPID_BYTES, &pos) &&
+        rep->index->rows(pos, T, rep->rows.data() + i * T)) {
+      compact = compact && rep->index->two_spans(pos, T, rep->spans.data() + 3 * i);
+    } else {
+      for (int64_t j = 0; j < T; ++j) rep->rows[i * T + j] = -1;
+      compact = false;
+    }
+  }
+  // A bound handle writes its own owner's windows only.
+  if (cut_foreign(rep, rep->rows.data(), B * T, T)) compact = false;
+  // The reference applies batch rows one after another (replay.py:139-149),
+  // so when sampled windows overlap the LAST writer of a step wins.  One
+  // launch has no order.  Usual case: no two windows share a pool row (checked
+  // on the sorted runs) and the windows travel as spans in the kernel
+  // arguments.  Otherwise drop all but the last occurrence of every pool row.
+  if (compact) {
+    auto& runs = rep->runs;
+    runs.clear();
+    for (int64_t i = 0; i < B; ++i) {
+      const int32_t* sp = rep->spans.data() + 3 * i;
+      runs.emplace_back(sp[0], sp[0] + sp[1]);
+      if (sp[1] < T) runs.emplace_back(sp[2], sp[2] + static_cast<int32_t>(T) - sp[1]);
+    }
+    std::sort(runs.begin(), runs.end());
+    for (size_t i = 1; i < runs.size() && compact; ++i) compact = runs[i].first >= runs[i - 1].second;
+  }
+  if (!compact) {
+    rep->spans.clear();
+    const size_t pool_rows = static_cast<size_t>(rep->index->config().n_slots * rep->index->config().chunksize);
+    if (rep->stamp.size() < pool_rows) rep->stamp.resize(pool_rows, 0);
+    if (++rep->stamp_epoch == 0) {       // wrapped: start over
+      std::fill(rep->stamp.begin(), rep->stamp.end(), 0u);
+      rep->stamp_epoch = 1;
+    }
+    for (int64_t i = B * T - 1; i >= 0; --i) {
+      const int32_t row = rep->rows[i];
+      if (row < 0) continue;
+      if (rep->stamp[row] == rep->stamp_epoch) rep->rows[i] = -1;
+      else rep->stamp[row] = rep->stamp_epoch;
+    }
+  }
+  rep->timing_update = rep->timer_update.enabled;
+  try {
+    run_move_all(rep, list, rep->rows.data(), B * T, nullptr, false, stream, &rep->spans);
+  } catch (...) {
+    rep->timing_update = false;
+    throw;
+  }
+  rep->timing_update = false;
+}
+
 int32_t emb_replay_update(emb_replay_t* rep, int64_t B, int64_t T, const uint8_t* stepids,
                           int32_t n_keys, const int32_t* key_ids, const void* const* src,
                           void* stream) {
-  REP_OP({
-    need(B >= 0 && T >= 1 && stepids, "update: bad arguments");
-    settle_carry(rep);
-    if (B == 0) return;
-    KeyList list = list_subset(rep, n_keys, key_ids, src);
-    list.seq_len = static_cast<int32_t>(T);
-    rep->rows.resize(B * T);
-    rep->spans.resize(3 * B);
-    bool compact = true;    // every window resolved into at most two runs of pool rows
-    for (int64_t i = 0; i < B; ++i) {
-      emb::ReplayIndex::Pos pos;
-      if (rep->index->parse_stepid(stepids + i * EMB_STEPID_BYTES, &pos) &&
-          rep->index->rows(pos, T, rep->rows.data() + i * T)) {
-        compact = compact && rep->index->two_spans(pos, T, rep->spans.data() + 3 * i);
-      } else {
-        for (int64_t j = 0; j < T; ++j) rep->rows[i * T + j] = -1;
-        compact = false;
-      }
-    }
-    // The reference applies batch rows one after another (replay.py:139-149),
-    // so when sampled windows overlap the LAST writer of a step wins.  One
-    // launch has no order.  Usual case: no two windows share a pool row (checked
-    // on the sorted runs) and the windows travel as spans in the kernel
-    // arguments.  Otherwise drop all but the last occurrence of every pool row.
-    if (compact) {
-      auto& runs = rep->runs;
-      runs.clear();
-      for (int64_t i = 0; i < B; ++i) {
-        const int32_t* sp = rep->spans.data() + 3 * i;
-        runs.emplace_back(sp[0], sp[0] + sp[1]);
-        if (sp[1] < T) runs.emplace_back(sp[2], sp[2] + static_cast<int32_t>(T) - sp[1]);
-      }
-      std::sort(runs.begin(), runs.end());
-      for (size_t i = 1; i < runs.size() && compact; ++i) compact = runs[i].first >= runs[i - 1].second;
-    }
-    if (!compact) {
-      rep->spans.clear();
-      const size_t pool_rows = static_cast<size_t>(rep->index->config().n_slots * rep->index->config().chunksize);
-      if (rep->stamp.size() < pool_rows) rep->stamp.resize(pool_rows, 0);
-      if (++rep->stamp_epoch == 0) {       // wrapped: start over
-        std::fill(rep->stamp.begin(), rep->stamp.end(), 0u);
-        rep->stamp_epoch = 1;
-      }
-      for (int64_t i = B * T - 1; i >= 0; --i) {
-        const int32_t row = rep->rows[i];
-        if (row < 0) continue;
-        if (rep->stamp[row] == rep->stamp_epoch) rep->rows[i] = -1;
-        else rep->stamp[row] = rep->stamp_epoch;
-      }
-    }
-    rep->timing_update = rep->timer_update.enabled;
-    try {
-      run_move_all(rep, list, rep->rows.data(), B * T, nullptr, false, static_cast<hipStream_t>(stream),
-                   &rep->spans);
-    } catch (...) {
-      rep->timing_update = false;
-      throw;
-    }
-    rep->timing_update = false;
-  });
+  REP_OP(update_locked(rep, B, T, stepids, n_keys, key_ids, src, 0, 0, static_cast<hipStream_t>(stream)));
+}
+
+int32_t emb_replay_update_grouped(emb_replay_t* rep, int64_t B, int64_t T, const uint8_t* first_stepids,
+                                  int32_t n_keys, const int32_t* key_ids, const void* const* src,
+                                  int32_t group, int64_t group_stride, void* stream) {
+  REP_OP(update_locked(rep, B, T, first_stepids, n_keys, key_ids, src, group, group_stride,
+                       static_cast<hipStream_t>(stream)));
 }
 
 int32_t emb_replay_gather_rows(emb_replay_t* rep, const int32_t* rows, int64_t n_rows,
@@ -852,6 +919,7 @@ int32_t emb_replay_gather_rows(emb_replay_t* rep, const int32_t* rows, int64_t n
     }
     list.seq_len = static_cast<int32_t>(seq_len);
     if (list.key.empty()) return;
+    rows = owned_table(rep, rows, n_rows, seq_len);
     // Sequences that are at most two contiguous runs of pool rows (windows that
     // cross one chunk boundary) travel as {row0, count0, row1} in the kernel
     // arguments instead of a row table in device memory.
@@ -886,6 +954,7 @@ int32_t emb_replay_scatter_rows(emb_replay_t* rep, const int32_t* rows, int64_t 
     settle_carry(rep);
     if (n_rows == 0) return;
     KeyList list = list_subset(rep, n_keys, key_ids, src);
+    rows = owned_table(rep, rows, n_rows, 1);
     run_move_all(rep, list, rows, n_rows, nullptr, false, static_cast<hipStream_t>(stream));
   });
 }

@@ -425,7 +425,9 @@ class ShardedReplay:
   of its own env block.  `sample` gathers the sequences this rank owns into
   their final positions of a zero-filled packed (B, L, S) buffer and one RCCL
   all-reduce(sum) — supports are disjoint, so the sum is a merge — leaves the
-  full batch on every rank.
+  full batch on every rank.  `update` writes agent outputs and priorities back
+  (replay.py:129-149); the replay's handle is bound to this rank's owner, so it
+  plans no pool access outside this rank's slot range.
   """
 
   def __init__(self, length, capacity, envs_per_rank, rank=None, world=None,
@@ -446,6 +448,8 @@ class ShardedReplay:
     self.replay = Replay(
         length, capacity, owners=self.world, owner=self.rank,
         workers_per_owner=envs_per_rank, slots=slots, **kwargs)
+    from ._lib import api
+    api.emb_replay_bind_owner(self.replay._handle, self.rank)
     self.length = self.replay.length
 
   def __len__(self):
@@ -513,6 +517,107 @@ class ShardedReplay:
           rep._handle, _lib.ptr(rows), rows.size, rep.length, ptrs, rep._stream())
     self._reduce(flat)
     return views
+
+  def update(self, data, sliced=False, gather=None):
+    """Write agent outputs back over sampled steps and/or re-prioritise
+    (replay.py:129-149), called on every rank in lockstep.  Results equal one
+    Replay over all envs given the whole batch.
+
+    sliced=False: `data` is the whole sampled batch (B, T, ...) on every rank;
+    each rank writes the windows it owns, no collective.
+    sliced=True: `data` is this rank's DP slice, sequences [r*B/n, (r+1)*B/n)
+    in `sample`'s order.  Step ids, priorities and the written keys are packed
+    into one buffer, ONE all-gather hands every rank all slices in rank order,
+    and one grouped write-back reads the whole batch straight out of the
+    receive buffer.  `gather(flat) -> (world * flat.numel(),) uint8`: default
+    the process group (async_all_gather); a NativeComm / DirectComm, whose
+    `all_gather` has that form, is accepted too.
+
+    T < length works as in Replay.update: the windows start at stepid[:, 0]
+    (DreamerV3 writes its latents back with stepid[:, K:],
+    dreamerv3/agent.py:333).  Priorities reach the replicated selector in the
+    global batch order on every rank."""
+    if not sliced:
+      return self.replay.update(data)
+    import ctypes as C
+    from . import _lib
+    from ._lib import api
+    rep = self.replay
+    data = dict(data)
+    stepid = torch.as_tensor(data.pop('stepid'))
+    priority = data.pop('priority', None)
+    assert stepid.ndim == 3 and stepid.shape[-1] == _lib.STEPID_BYTES, stepid.shape
+    part, T = int(stepid.shape[0]), int(stepid.shape[1])
+    specs = [('stepid', torch.uint8, (_lib.STEPID_BYTES,))]
+    values = [stepid]
+    if priority is not None:
+      priority = torch.as_tensor(priority)
+      assert tuple(priority.shape) == (part, T), priority.shape
+      specs.append(('priority', priority.dtype, ()))
+      values.append(priority)
+    ids = (C.c_int32 * max(1, len(data)))()
+    for j, (name, value) in enumerate(data.items()):
+      key = rep._keys[rep._keyid[name]]
+      value = torch.as_tensor(value)
+      if tuple(value.shape) != (part, T, *key.shape):
+        raise ValueError((name, tuple(value.shape), (part, T, *key.shape)))
+      specs.append((name, key.dtype, key.shape))
+      values.append(value)
+      ids[j] = rep._keyid[name]
+    layout = PackedLayout(specs, part, T)
+    flat = torch.empty(layout.nbytes, dtype=torch.uint8, device=rep.device)
+    for (name, *_), value in zip(specs, values):
+      layout.view(flat, name).copy_(value)
+    if gather is None:
+      gather = self._all_gather
+    elif hasattr(gather, 'all_gather'):
+      gather = gather.all_gather
+    out = gather(flat)
+    assert out.dtype == torch.uint8 and out.numel() == self.world * layout.nbytes, (out.dtype, out.shape)
+    out = out.reshape(self.world, layout.nbytes)
+    B = self.world * part
+    sid = layout.view(out, 'stepid').reshape(B, T, _lib.STEPID_BYTES)
+    with rep._lock:
+      rep._flush()
+      if priority is not None:
+        if not hasattr(rep.sampler, 'prioritize'):
+          raise AttributeError(       # what replay.py:137 raises
+              f'{type(rep.sampler).__name__!r} object has no attribute '
+              "'prioritize'")
+        flat_sid = np.ascontiguousarray(sid.cpu().numpy().reshape(-1, _lib.STEPID_BYTES))
+        prios = np.ascontiguousarray(
+            layout.view(out, 'priority').cpu().numpy(), np.float64).reshape(-1)
+        api.emb_replay_prioritize(rep._handle, _lib.ptr(flat_sid), _lib.ptr(prios), len(prios))
+        rep._reraise()
+      if data:
+        first = np.ascontiguousarray(sid[:, 0].cpu().numpy())
+        base = out.data_ptr()
+        ptrs = (C.c_void_p * len(data))(*[base + layout.index[name][3] for name in data])
+        # sequence s of the global batch: sequence s % part of slice s // part
+        api.emb_replay_update_grouped(
+            rep._handle, B, T, _lib.ptr(first), len(data), ids, ptrs, part, layout.nbytes,
+            rep._stream())
+      rep._updates += B * T        # replay.py:134, the global batch as one replay counts it
+
+  def _all_gather(self, flat):
+    out = torch.empty(self.world * flat.numel(), dtype=torch.uint8, device=flat.device)
+    if self.world == 1:
+      out.copy_(flat)
+    else:
+      async_all_gather(out, flat).wait()
+    return out
+
+  def stats(self):
+    """replay.py:58-74.  Every count comes from the replicated index (what one
+    replay over all envs reports); `ram_gb` is what this rank's pool holds: the
+    index's chunks in this rank's slot range."""
+    rep = self.replay
+    out = rep.stats()
+    per = rep._slots // self.world
+    mine = sum(1 for chunk in rep._chunk_table() if chunk['slot'] // per == self.rank)
+    rowbytes = sum(k.rowbytes for k in rep._keys) if rep._keys else 0
+    out['ram_gb'] = mine * rep.chunksize * rowbytes / 1024 ** 3
+    return out
 
 
 class GlobalClock:

@@ -336,6 +336,28 @@ int32_t emb_replay_sample_grouped(emb_replay_t* rep, int64_t batch, int32_t mode
 int32_t emb_replay_update(emb_replay_t* rep, int64_t B, int64_t T, const uint8_t* stepids,
                           int32_t n_keys, const int32_t* key_ids, const void* const* src,
                           void* stream);
+/* emb_replay_update (replay.py:129-149: stepids = the B first step ids
+ * stepid[i, 0], decoded on the host; a window whose chunk was evicted is
+ * skipped; where windows overlap the last occurrence wins) with the source in
+ * the grouped layout of emb_replay_sample_grouped: sequence s of key k is read
+ * from src[k] + (s / group) * group_stride + (s % group) * T * rowbytes[k]
+ * (group_stride a multiple of 16; group = 0: identical to emb_replay_update).
+ * The layout an all-gather of per-rank packed slices delivers: every rank
+ * writes the whole batch back with one launch straight from the receive
+ * buffer (replay.py:129-149 run on the global batch, as the reference's
+ * train step does after assembling it, embodied/jax/internal.py:145-152).    */
+int32_t emb_replay_update_grouped(emb_replay_t* rep, int64_t B, int64_t T,
+                                  const uint8_t* first_stepids, int32_t n_keys,
+                                  const int32_t* key_ids, const void* const* src, int32_t group,
+                                  int64_t group_stride, void* stream);
+/* Sharded pools (owners > 1): this process holds owner `owner`'s slot range of
+ * the pool only (set_keys received a virtual base).  A bound handle treats every
+ * window outside that range as rows -1 in the write-backs and gathers it plans
+ * (emb_replay_sample*, emb_replay_update*, emb_replay_gather_rows,
+ * emb_replay_scatter_rows): nothing is read or written there and the window's
+ * destination bytes are left as they are.  A window is one worker's chunk
+ * chain (replay.py:77-118), so it never spans owners.  owner = -1 unbinds.   */
+int32_t emb_replay_bind_owner(emb_replay_t* rep, int64_t owner);
 /* Move rows given an explicit host row table (multi-GPU owner-side gather,
  * fused sample+windowing, load from disk).  gather: a NULL dst[k] skips key k;
  * the flag annotation applies per `seq_len` rows.                             */
