@@ -188,6 +188,8 @@ SIGNATURES = {
     'emb_scan_director': [p, p, p, i64, i64, f32, f32, p, p],
     'emb_abstract_traj': [p, p, i64, i64, i32, p, p, p],
     'emb_synth_env_step': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p],
+    'emb_synth_env_step_masked': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p, p, i64, i32, p],
+    'emb_env_mask_supported': [i64, i32],
     'emb_comm_unique_id': [p],
     'emb_comm_init': [p, i32, i32, pp],
     'emb_comm_allgather_traj': [p, p, p, i64, p],
@@ -303,7 +305,7 @@ class _FastApi:
   arrays.  Same status handling as `api`."""
 
   SHAPES = {
-      'emb_synth_env_step': 'ints', 'emb_mask_actions': 'ints',
+      'emb_synth_env_step': 'ints', 'emb_mask_actions': 'ints', 'emb_synth_env_step_masked': 'ints',
       'emb_replay_add': 'ints', 'emb_replay_add_masked': 'ints',
       'emb_replay_obs_stack_insert': 'ints', 'emb_replay_publish': 'ints',
       'emb_replay_sample': 'ints', 'emb_replay_sample_grouped': 'ints', 'emb_replay_update': 'ints',

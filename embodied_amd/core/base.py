@@ -67,6 +67,34 @@ class Env:
     return f'{name}(obs_space={self.obs_space}, act_space={self.act_space})'
 
 
+class BatchEnv:
+  """A device-resident vector env (`Driver(batch_env=env, device='cuda')`):
+  `len(env)` envs behind one `step(acts) -> dict of (N, ...) device tensors`,
+  `acts` holding (N, ...) tensors and `reset`.  The reference's Driver masks the
+  policy's actions with `~is_last` before the env sees them (driver.py:72-75);
+  two optional attributes say how else the env can be served:
+
+  * `takes_unmasked_actions = True`: the env ignores the action of an env it
+    resets and is handed the policy's action tensors as they are.
+  * `masks_actions_in_step = True`: the env's own step launch makes the masked
+    copy.  The Driver then calls `step(acts, unmasked)`: `unmasked` maps the
+    (single) action key to the policy's raw tensor, `acts[key]` is the tensor
+    the masked values belong in and `acts['reset']` holds the flags.  The launch
+    stores `unmasked[key] * ~acts['reset']`, a multiply in the key's dtype, to
+    `acts[key]` and uses nothing but that product.  `step(acts)` without the
+    second argument receives masked actions as ever (the Driver settles a
+    pending mask itself when somebody reads `driver.acts`)."""
+
+  takes_unmasked_actions = False
+  masks_actions_in_step = False
+
+  def __len__(self):
+    raise NotImplementedError('Returns: number of envs')
+
+  def step(self, acts, unmasked=None):
+    raise NotImplementedError('Returns: dict of (N, ...) device tensors')
+
+
 class Stream:
   """An iterator whose position can be checkpointed."""
 

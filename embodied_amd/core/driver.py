@@ -197,7 +197,9 @@ class Driver:
     self.callbacks = []
     self.batch_callbacks = []
     self._sinks = []          # per registered callback: its Replay if it is a bare Replay.add
-    self.acts = None
+    self._acts = None         # what `acts` returns; the stepping loop uses this name
+    self._pending = None      # raw actions the env's next step launch has yet to mask into _acts
+    self._env_masks = False
     self.carry = None
     self._slab = {}
     self._obs_names, self._obs_has_logs = None, False
@@ -208,19 +210,70 @@ class Driver:
     self._workers.setflags(write=False)     # lets Replay.add_batch keep its converted copy
     self.reset()
 
+  @property
+  def acts(self):
+    """The next step's actions, masked (driver.py:72-75), and `reset`.  With an
+    env whose step launch masks its actions the masked values of the last step
+    do not exist before that launch: a reader in between gets them from a mask
+    launch of their own (`emb_mask_actions`), made here, once -- the env's next
+    step then takes them as they are.  The stepping loop never comes here."""
+    if self._pending is not None:
+      self._settle_pending()
+    return self._acts
+
+  @acts.setter
+  def acts(self, value):
+    self._pending = None
+    self._acts = value
+
+  def _settle_pending(self):
+    pending, self._pending = self._pending, None
+    flags = self._acts['reset']
+    stream = _lib.raw_stream(self.device)
+    for k, v in pending.items():
+      n = v.shape[0]
+      fast.emb_mask_actions(v.data_ptr(), self._acts[k].data_ptr(), n, v.numel() // n,
+                            _DTYPE_CODE[v.dtype], flags.data_ptr(), stream)
+
+  def _mask_dst(self, acts):
+    """Env-masked form: the set of the four-deep ring of masked-action buffers
+    that the env's next step launch fills from `acts`, or None if these actions
+    cannot travel that way (more than one key, a row the launch does not take,
+    a strided tensor): that step takes the three-launch path."""
+    if len(acts) != 1:
+      return None
+    names = tuple(acts)
+    ring = self._mask_ring
+    if ring is None or ring[0] != names:
+      ring = self._mask_ring = (names, [{} for _ in range(4)], [0])
+    ring[2][0] = turn = (ring[2][0] + 1) & 3
+    slot = ring[1][turn]
+    for k, v in acts.items():
+      if not v.is_contiguous():
+        return None
+      out = slot.get(k)
+      if out is None or out.dtype is not v.dtype or out.shape != v.shape:
+        code = _DTYPE_CODE.get(v.dtype)
+        if (code is None or v.ndim < 1 or v.shape[0] != self.length or v.numel() == 0
+            or not api.emb_env_mask_supported.raw(v.numel() // self.length * v.element_size(), code)):
+          return None
+        slot[k] = _lib.empty(v.shape, v.dtype, self.device)
+    return slot
+
   # driver.py:34-39
   def reset(self, init_policy=None):
+    self._pending = None
     if self.batch_env is not None:
-      self.acts = {
+      self._acts = {
           k: torch.zeros((self.length, *v.shape), dtype=replaylib._TORCH_OF[np.dtype(v.dtype)],
                          device=self.device)
           for k, v in self.act_space.items()}
-      self.acts['reset'] = torch.ones(self.length, dtype=torch.bool, device=self.device)
+      self._acts['reset'] = torch.ones(self.length, dtype=torch.bool, device=self.device)
     else:
-      self.acts = {
+      self._acts = {
           k: np.zeros((self.length,) + tuple(v.shape), v.dtype)
           for k, v in self.act_space.items()}
-      self.acts['reset'] = np.ones(self.length, bool)
+      self._acts['reset'] = np.ones(self.length, bool)
     self._acts_on_host = None          # actions fetched ahead belong to the old episode
     self._acts_flag_want = 0
     self.carry = init_policy and init_policy(self.length)
@@ -374,7 +427,7 @@ class Driver:
   def _step(self, policy, step, episode):
     if self.batch_env is not None:
       return self._step_device_env(policy, step, episode)
-    acts = self.acts
+    acts = self._acts
     assert all(len(x) == self.length for x in acts.values())
     host = self._acts_on_host
     if host is not None:
@@ -415,12 +468,12 @@ class Driver:
       # (`reset` may alias the step's is_last, as with a device vector env: device flags
       # are never mutated in place, and with the rotating upload buffers the tensor lives
       # four steps -- user callbacks, which may keep it, get fresh tensors every step)
-      self.acts = {**acts, 'reset': is_last if self._rotate() else is_last.clone()}
+      self._acts = {**acts, 'reset': is_last if self._rotate() else is_last.clone()}
     else:
       ended = is_last
       if ended.any():
         acts = {k: mask_actions(v, is_last) for k, v in acts.items()}
-      self.acts = {**acts, 'reset': is_last.copy()}
+      self._acts = {**acts, 'reset': is_last.copy()}
     if self.device is not None:
       self._fetch_acts()
       if self._upload_pending == 'unrecorded':
@@ -466,16 +519,16 @@ class Driver:
     `reset` is the step's `is_last`, which the host has already.  The first step
     checks the stores against a plain copy and keeps the copies if they differ
     (a pinned allocation the GPU cannot address)."""
-    if not all(torch.is_tensor(v) and v.is_cuda for v in self.acts.values()):
+    if not all(torch.is_tensor(v) and v.is_cuda for v in self._acts.values()):
       self._acts_on_host = None
       return
     host = {}
     flags = getattr(self, '_host_flags', {}).get('is_last')
-    reset = self.acts.get('reset')
+    reset = self._acts.get('reset')
     by_store = getattr(self, '_acts_by_store', None)
     stream = None
     stored_all, last_store = True, None
-    for k, v in self.acts.items():
+    for k, v in self._acts.items():
       if k == 'reset' and flags is not None:
         host[k] = flags.copy()
         continue
@@ -534,7 +587,13 @@ class Driver:
     """Same step with a device-resident vector env: nothing is read back, so
     the mask runs unconditionally (a no-op where nothing ended) and episodes
     are counted only when the caller stops on them."""
-    obs = self.batch_env.step(self.acts)
+    pending = self._pending
+    if pending is None:
+      obs = self.batch_env.step(self._acts)
+    else:
+      # (env-masked form: this launch stores pending * ~reset into _acts' tensors)
+      self._pending = None
+      obs = self.batch_env.step(self._acts, pending)
     names = tuple(obs)
     if names != self._obs_names:          # which keys are 'log/*' is looked at once per key set
       self._obs_names = names
@@ -579,9 +638,30 @@ class Driver:
             and hasattr(sink, 'carry_publish') and hasattr(sink, 'add_step'))
         if self._unmasked:
           sink.carry_publish(True)
+        # An env whose step launch masks its actions itself (`masks_actions_in_step`,
+        # base.py) still receives masked actions -- the reference's form -- but no
+        # launch of ours makes them: the raw actions are remembered for the env's
+        # next step, which stores value * ~is_last into the ring's buffers, and the
+        # pool write is the Replay's carried publish.  Two dependent launches.
+        self._env_masks = bool(
+            not self._unmasked and _CARRY and not self._fresh_obs
+            and getattr(self.batch_env, 'masks_actions_in_step', False)
+            and hasattr(sink, 'carry_publish') and hasattr(sink, 'add_step'))
+        if self._env_masks:
+          sink.carry_publish(True)
+      if self._env_masks and not self._unmasked:
+        dst = self._mask_dst(acts)
+        if dst is not None:
+          sink.add_step(obs, acts, outs, self._workers, is_last, False)
+          self._acts = {**dst, 'reset': is_last}
+          self._pending = acts        # (kept until the env launch that masks them is issued)
+          step += self.length
+          if self._count_episodes:
+            episode += int(is_last.sum().item())
+          return step, episode
       if self._unmasked:
         sink.add_step(obs, acts, outs, self._workers, is_last, False)
-        self.acts = {**acts, 'reset': is_last}
+        self._acts = {**acts, 'reset': is_last}
         step += self.length
         if self._count_episodes:
           episode += int(is_last.sum().item())
@@ -599,11 +679,11 @@ class Driver:
         acts = sink.add_step(obs, acts, outs, self._workers, is_last, mask[2])
       else:
         acts = sink.add_batch({**obs, **acts, **outs}, self._workers, mask=mask)
-      self.acts = {**acts, 'reset': is_last}
+      self._acts = {**acts, 'reset': is_last}
     else:
       acts = {k: mask_actions(v, is_last) for k, v in acts.items()}
       # Device flags are never mutated in place: `reset` may alias is_last.
-      self.acts = {**acts, 'reset': is_last}
+      self._acts = {**acts, 'reset': is_last}
       self._dispatch({**obs, **acts, **outs, **logs})
     step += self.length
     if self._count_episodes:

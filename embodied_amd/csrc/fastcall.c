@@ -69,11 +69,11 @@ static int as_float(PyObject* o, float* out) {
   return 0;
 }
 
-#define MAX_INTS 14
+#define MAX_INTS 17
 
 static PyObject* call_ints(PyObject* self, PyObject* const* args, Py_ssize_t nargs) {
   if (nargs < 1 || nargs > MAX_INTS + 1) {
-    PyErr_SetString(PyExc_TypeError, "fastcall.ints(addr, up to 14 arguments)");
+    PyErr_SetString(PyExc_TypeError, "fastcall.ints(addr, up to 17 arguments)");
     return NULL;
   }
   u64 a[MAX_INTS + 1] = {0};
@@ -99,6 +99,9 @@ static PyObject* call_ints(PyObject* self, PyObject* const* args, Py_ssize_t nar
     case 12: status = ((int32_t(*)(u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64))fn)(a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11], a[12]); break;
     case 13: status = ((int32_t(*)(u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64))fn)(a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11], a[12], a[13]); break;
     case 14: status = ((int32_t(*)(u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64))fn)(a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11], a[12], a[13], a[14]); break;
+    case 15: status = ((int32_t(*)(u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64))fn)(a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11], a[12], a[13], a[14], a[15]); break;
+    case 16: status = ((int32_t(*)(u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64))fn)(a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11], a[12], a[13], a[14], a[15], a[16]); break;
+    case 17: status = ((int32_t(*)(u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64, u64))fn)(a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11], a[12], a[13], a[14], a[15], a[16], a[17]); break;
     default: status = -1; break;
   }
   Py_END_ALLOW_THREADS

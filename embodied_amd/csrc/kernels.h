@@ -180,6 +180,22 @@ hipError_t launch_synth_env(uint8_t* image, float* reward, uint8_t* is_first,
                             int64_t frame_bytes, int64_t env0, int64_t episode_len,
                             const uint8_t* reset, int32_t* counters, int turn,
                             hipStream_t stream);
+// The same step with a mask job: the launch also stores `act * !reset[e]` (in
+// `dtype`, rows of `rowbytes` bytes; the keys carry_supported accepts) to
+// `masked_out`, the env's input as the Driver defines it.  synth_mask_job fills
+// `job` (kSynthJobBytes of HOST memory) and says whether the preloaded form can
+// run: true = copy the block to device memory and pass its address as job_dev;
+// false = the flag buffers are too far from `reward`, pass job_dev = null (the
+// job then travels by value with the far kernel).
+constexpr size_t kSynthJobBytes = 48;
+bool synth_mask_job(void* job, const void* act, void* masked_out, int64_t rowbytes, int dtype,
+                    const float* reward, const uint8_t* is_first, const uint8_t* is_last,
+                    const uint8_t* is_terminal);
+hipError_t launch_synth_env_masked(uint8_t* image, float* reward, uint8_t* is_first,
+                                   uint8_t* is_last, uint8_t* is_terminal, int64_t n,
+                                   int64_t frame_bytes, int64_t env0, int64_t episode_len,
+                                   const uint8_t* reset, int32_t* counters, int turn,
+                                   const void* job_host, const void* job_dev, hipStream_t stream);
 
 // Obs stack fused with the early part of Replay.add (driver.py:65 +
 // jax/agent.py:230 + chunk.py:41-50): every frame is read once and written to

@@ -419,18 +419,47 @@ __device__ __forceinline__ void gather_block(const MoveArgs& a, const MoveTables
 // `value * mask.astype(value.dtype)` (driver.py:84-87) — to the pool row and to
 // the masked-action buffer.
 template <typename T>
-__device__ __forceinline__ void put_masked(const uint8_t* src, uint8_t* pool, uint8_t* out, bool keep) {
+__device__ __forceinline__ T put_masked(const uint8_t* src, uint8_t* pool, uint8_t* out, bool keep) {
   const T v = gload<T>(src) * static_cast<T>(keep ? 1 : 0);
   if (pool) gstore<T>(pool, v);
   if (out) gstore<T>(out, v);
+  return v;
 }
 
-__device__ __forceinline__ void put_masked_bf16(const uint8_t* src, uint8_t* pool, uint8_t* out, bool keep) {
+__device__ __forceinline__ uint16_t put_masked_bf16(const uint8_t* src, uint8_t* pool, uint8_t* out, bool keep) {
   // Widen to f32 (exact), multiply, narrow: the product is x, +-0 or NaN.
   const float x = __uint_as_float(static_cast<uint32_t>(gload<uint16_t>(src)) << 16);
   const uint16_t v = static_cast<uint16_t>(__float_as_uint(x * (keep ? 1.f : 0.f)) >> 16);
   if (pool) gstore<uint16_t>(pool, v);
   if (out) gstore<uint16_t>(out, v);
+  return v;
+}
+
+// The same by dtype code: THE definition of `value * ~flag` for every launch that
+// masks an action (the movers, the publish launch, the carried publish, a device
+// env's step).  Returns the product's bits, zero-extended, for a caller that goes
+// on computing with the masked value.
+template <typename T>
+__device__ __forceinline__ uint64_t masked_bits(T v) {
+  static_assert(sizeof(T) <= 8, "a masked element fits 64 bits");
+  uint64_t bits = 0;
+  __builtin_memcpy(&bits, &v, sizeof(T));
+  return bits;
+}
+
+__device__ __forceinline__ uint64_t put_masked_as(int dtype, const uint8_t* src, uint8_t* pool, uint8_t* out,
+                                                  bool keep) {
+  switch (dtype) {
+    case kU8: case kBool: return masked_bits(put_masked<uint8_t>(src, pool, out, keep));
+    case kI8: return masked_bits(put_masked<int8_t>(src, pool, out, keep));
+    case kI16: return masked_bits(put_masked<int16_t>(src, pool, out, keep));
+    case kI32: return masked_bits(put_masked<int32_t>(src, pool, out, keep));
+    case kI64: return masked_bits(put_masked<int64_t>(src, pool, out, keep));
+    case kF16: return masked_bits(put_masked<_Float16>(src, pool, out, keep));
+    case kBF16: return masked_bits(put_masked_bf16(src, pool, out, keep));
+    case kF32: return masked_bits(put_masked<float>(src, pool, out, keep));
+    default: return masked_bits(put_masked<double>(src, pool, out, keep));
+  }
 }
 
 template <bool kLds = false>
@@ -448,17 +477,7 @@ __device__ __forceinline__ void scatter_masked(const MoveArgs& a, const MoveTabl
   const uint8_t* src = key.batch + r * key.rowbytes + off;
   uint8_t* pool = row >= 0 ? key.pool + row * key.rowbytes + off : nullptr;
   uint8_t* out = tb.mask_out[k] ? tb.mask_out[k] + r * key.rowbytes + off : nullptr;
-  switch (tb.mask_dtype[k]) {
-    case kU8: case kBool: put_masked<uint8_t>(src, pool, out, keep); break;
-    case kI8: put_masked<int8_t>(src, pool, out, keep); break;
-    case kI16: put_masked<int16_t>(src, pool, out, keep); break;
-    case kI32: put_masked<int32_t>(src, pool, out, keep); break;
-    case kI64: put_masked<int64_t>(src, pool, out, keep); break;
-    case kF16: put_masked<_Float16>(src, pool, out, keep); break;
-    case kBF16: put_masked_bf16(src, pool, out, keep); break;
-    case kF32: put_masked<float>(src, pool, out, keep); break;
-    default: put_masked<double>(src, pool, out, keep); break;
-  }
+  put_masked_as(tb.mask_dtype[k], src, pool, out, keep);
 }
 
 // batch[r] -> pool[rows[r]]; rows[r] < 0 are skipped (evicted update targets).
@@ -1137,17 +1156,7 @@ __device__ __forceinline__ void prewrite_carry(const PreTable& t, const uint32_t
   const bool keep = gload<uint8_t>(c.flags + prev) == 0;
   const uint8_t* src = c.src + n * c.rowbytes + off;
   uint8_t* pool = c.pool + prev * c.rowbytes + off;
-  switch (c.dtype) {
-    case kU8: case kBool: put_masked<uint8_t>(src, pool, nullptr, keep); break;
-    case kI8: put_masked<int8_t>(src, pool, nullptr, keep); break;
-    case kI16: put_masked<int16_t>(src, pool, nullptr, keep); break;
-    case kI32: put_masked<int32_t>(src, pool, nullptr, keep); break;
-    case kI64: put_masked<int64_t>(src, pool, nullptr, keep); break;
-    case kF16: put_masked<_Float16>(src, pool, nullptr, keep); break;
-    case kBF16: put_masked_bf16(src, pool, nullptr, keep); break;
-    case kF32: put_masked<float>(src, pool, nullptr, keep); break;
-    default: put_masked<double>(src, pool, nullptr, keep); break;
-  }
+  put_masked_as(c.dtype, src, pool, nullptr, keep);
 }
 
 __device__ __forceinline__ void prewrite_narrow(const PrewriteArgs& a, int64_t n) {
@@ -1282,17 +1291,7 @@ __global__ __launch_bounds__(kThreads) void publish_one_kernel(
   const uint8_t* src = a.src + r * a.rowbytes + off;
   uint8_t* pool = row >= 0 ? a.pool + row * a.rowbytes + off : nullptr;
   uint8_t* out = a.out ? a.out + r * a.rowbytes + off : nullptr;
-  switch (a.dtype & 0xFF) {
-    case kU8: case kBool: put_masked<uint8_t>(src, pool, out, keep); break;
-    case kI8: put_masked<int8_t>(src, pool, out, keep); break;
-    case kI16: put_masked<int16_t>(src, pool, out, keep); break;
-    case kI32: put_masked<int32_t>(src, pool, out, keep); break;
-    case kI64: put_masked<int64_t>(src, pool, out, keep); break;
-    case kF16: put_masked<_Float16>(src, pool, out, keep); break;
-    case kBF16: put_masked_bf16(src, pool, out, keep); break;
-    case kF32: put_masked<float>(src, pool, out, keep); break;
-    default: put_masked<double>(src, pool, out, keep); break;
-  }
+  put_masked_as(a.dtype & 0xFF, src, pool, out, keep);
 }
 
 template <typename Out>
@@ -1858,6 +1857,85 @@ struct SynthArgs {
 };
 static_assert(sizeof(SynthArgs) <= 64, "synth_env_kernel's arguments (passed one by one, n from the grid) are preloaded");
 
+// Mask job: the env's launch stores `act * !reset[e]` (the policy's raw actions
+// times the flags the step itself restarts on: the Driver passes the previous
+// step's is_last as `reset`) to `out`, the Driver's masked-action buffer -- the
+// env's input as driver.py:72-75 defines it -- so that no launch of its own has
+// to make that copy.  src == null: no job.
+//
+// Where the job travels.  The preload covers 14 dwords (16 user SGPRs less the
+// two of the kernel-argument pointer; `.amdhsa_user_sgpr_kernarg_preload_length
+// 14` for synth_env_kernel) and the step's own arguments fill them: two more
+// pointers and the key's size would be fetched with s_load by EVERY wave, frame
+// workgroups included (the compiler puts the kernel-argument loads in front of
+// the first branch) -- with host-resident arguments a PCIe read in front of
+// every frame store.  So the masked form takes ONE pointer to a block in device
+// memory (written through the BAR like PreTable) in place of the three flag
+// offsets, which move into the block: 56 bytes, all preloaded, and only
+// workgroup 0 of an env -- the one that stores the masked values and the flags --
+// reads the block.  The frame workgroups run the same instructions as before.
+struct alignas(16) SynthMaskJob {
+  const uint8_t* src;         // (n, rowbytes) raw actions
+  uint8_t* out;               // (n, rowbytes) masked actions
+  int32_t rowbytes, dtype, elem;
+  int32_t off_first, off_last, off_terminal;   // bytes from `reward` (masked form only)
+};
+static_assert(sizeof(SynthMaskJob) == kSynthJobBytes, "kernels.h states the size of the block");
+
+struct SynthStep {
+  int32_t count;
+  bool restart, done;
+};
+
+__device__ __forceinline__ SynthStep synth_step(const SynthArgs& a, int64_t e) {
+  const int32_t n = a.n_turn >> 1, turn = a.n_turn & 1;
+  const int32_t* __restrict__ in = a.counters + turn * 2 * n;
+  int32_t count = in[2 * e];
+  const bool was_done = in[2 * e + 1] != 0;
+  const bool restart = (a.reset && a.reset[e]) || was_done;
+  const int64_t length = a.episode_len + ((a.env0 + e) % 8) * 13;
+  count = restart ? 0 : count + 1;
+  return {count, restart, !restart && count >= length};
+}
+
+// byte i of the frame = (salt + i) & 0xFF, written 16 bytes per lane.
+__device__ __forceinline__ void synth_frame(const SynthArgs& a, int64_t e, int32_t count, uint32_t blocks) {
+  const uint32_t salt = static_cast<uint32_t>((a.env0 + e) * 131 + static_cast<int64_t>(count) * 7);
+  u32x4* out = reinterpret_cast<u32x4*>(a.image + e * a.frame_bytes);
+  const int64_t vecs = a.frame_bytes >> 4;
+  auto word = [salt](int64_t byte0) {
+    const uint32_t x = salt + static_cast<uint32_t>(byte0);
+    return (x & 0xFF) | (((x + 1) & 0xFF) << 8) | (((x + 2) & 0xFF) << 16) | (((x + 3) & 0xFF) << 24);
+  };
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; i < vecs;
+       i += static_cast<int64_t>(blocks) * kThreads)
+    __builtin_nontemporal_store(
+        u32x4{word(i * 16), word(i * 16 + 4), word(i * 16 + 8), word(i * 16 + 12)}, out + i);
+}
+
+// Masked element `threadIdx.x` of env e's action row: stored to the job's `out`
+// and returned (bits, zero-extended) -- what a simulator goes on with; this
+// generator reads no action.  Called by workgroup 0 of the env only; one element
+// per lane (rowbytes / elem <= kThreads, carry_supported).
+__device__ __forceinline__ uint64_t synth_masked_action(const SynthMaskJob& j, const uint8_t* reset, int64_t e) {
+  const int64_t off = static_cast<int64_t>(threadIdx.x) * j.elem;
+  if (!j.src || off >= j.rowbytes) return 0;
+  const bool keep = !reset || gload<uint8_t>(reset + e) == 0;
+  return put_masked_as(j.dtype, j.src + e * j.rowbytes + off, nullptr, j.out + e * j.rowbytes + off, keep);
+}
+
+__device__ __forceinline__ void synth_bookkeeping(const SynthArgs& a, int64_t e, const SynthStep& s,
+                                                  uint8_t* is_first, uint8_t* is_last, uint8_t* is_terminal) {
+  const int32_t n = a.n_turn >> 1, turn = a.n_turn & 1;
+  int32_t* next = a.counters + (1 - turn) * 2 * n;
+  next[2 * e] = s.count;
+  next[2 * e + 1] = s.done ? 1 : 0;
+  a.reward[e] = s.restart ? 0.f : static_cast<float>(s.count % 7);
+  is_first[e] = s.restart ? 1 : 0;
+  is_last[e] = s.done ? 1 : 0;
+  is_terminal[e] = s.done ? 1 : 0;
+}
+
 __global__ __launch_bounds__(kThreads) void synth_env_kernel(
     int32_t* counters, const uint8_t* reset, uint8_t* image, float* reward, int32_t off_first,
     int32_t off_last, int32_t off_terminal, int32_t frame_bytes, int32_t env0, int32_t len_turn) {
@@ -1867,69 +1945,56 @@ __global__ __launch_bounds__(kThreads) void synth_env_kernel(
                     frame_bytes, env0, len_turn & 0x7FFFFFFF,
                     static_cast<int32_t>(gridDim.y << 1 | (static_cast<uint32_t>(len_turn) >> 31))};
   const int64_t e = blockIdx.y;
-  const int32_t n = a.n_turn >> 1, turn = a.n_turn & 1;
-  const int32_t* __restrict__ in = a.counters + turn * 2 * n;
-  int32_t count = in[2 * e];
-  const bool was_done = in[2 * e + 1] != 0;
-  const bool restart = (a.reset && a.reset[e]) || was_done;
-  const int64_t length = a.episode_len + ((a.env0 + e) % 8) * 13;
-  count = restart ? 0 : count + 1;
-  const bool done = !restart && count >= length;
-  const uint32_t salt = static_cast<uint32_t>((a.env0 + e) * 131 + static_cast<int64_t>(count) * 7);
-  // byte i of the frame = (salt + i) & 0xFF, written 16 bytes per lane.
-  u32x4* out = reinterpret_cast<u32x4*>(a.image + e * a.frame_bytes);
-  const int64_t vecs = a.frame_bytes >> 4;
-  auto word = [salt](int64_t byte0) {
-    const uint32_t x = salt + static_cast<uint32_t>(byte0);
-    return (x & 0xFF) | (((x + 1) & 0xFF) << 8) | (((x + 2) & 0xFF) << 16) | (((x + 3) & 0xFF) << 24);
-  };
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; i < vecs;
-       i += static_cast<int64_t>(gridDim.x) * kThreads)
-    __builtin_nontemporal_store(
-        u32x4{word(i * 16), word(i * 16 + 4), word(i * 16 + 8), word(i * 16 + 12)}, out + i);
+  const SynthStep s = synth_step(a, e);
+  synth_frame(a, e, s.count, gridDim.x);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    int32_t* next = a.counters + (1 - turn) * 2 * n;
-    next[2 * e] = count;
-    next[2 * e + 1] = done ? 1 : 0;
     uint8_t* flags = reinterpret_cast<uint8_t*>(a.reward);
-    a.reward[e] = restart ? 0.f : static_cast<float>(count % 7);
-    flags[a.off_first + e] = restart ? 1 : 0;
-    flags[a.off_last + e] = done ? 1 : 0;
-    flags[a.off_terminal + e] = done ? 1 : 0;
+    synth_bookkeeping(a, e, s, flags + a.off_first, flags + a.off_last, flags + a.off_terminal);
+  }
+}
+
+// The step with a mask job (see SynthMaskJob): 56 bytes of arguments, preloaded.
+// The grid's size travels in them too -- the env count as the 14th dword, the
+// workgroups per frame (1..4) less one in the low bits of the frame size, a
+// multiple of 16: gridDim is itself a (hidden) kernel argument behind the
+// preloaded ones, an s_load per wave in synth_env_kernel that this form does
+// not have.
+// `job` is DEVICE memory; workgroup 0 of an env reads it (uniform: scalar loads,
+// issued beside the loads of the env's state), stores its frame share, then the
+// masked action elements, one per lane, then the flags.
+__global__ __launch_bounds__(kThreads) void synth_env_masked_kernel(
+    int32_t* counters, const uint8_t* reset, uint8_t* image, float* reward,
+    const SynthMaskJob* __restrict__ job, int32_t frame_bytes, int32_t env0, int32_t len_turn, int32_t n_envs) {
+  const SynthArgs a{counters, reset, image, reward, 0, 0, 0,
+                    frame_bytes & ~15, env0, len_turn & 0x7FFFFFFF,
+                    static_cast<int32_t>(static_cast<uint32_t>(n_envs) << 1 | (static_cast<uint32_t>(len_turn) >> 31))};
+  const uint32_t blocks = (static_cast<uint32_t>(frame_bytes) & 15u) + 1;     // = gridDim.x
+  const int64_t e = blockIdx.y;
+  if (blockIdx.x != 0) {
+    synth_frame(a, e, synth_step(a, e).count, blocks);
+    return;
+  }
+  const SynthMaskJob j = *job;
+  const SynthStep s = synth_step(a, e);
+  synth_frame(a, e, s.count, blocks);
+  synth_masked_action(j, a.reset, e);
+  if (threadIdx.x == 0) {
+    uint8_t* flags = reinterpret_cast<uint8_t*>(a.reward);
+    synth_bookkeeping(a, e, s, flags + j.off_first, flags + j.off_last, flags + j.off_terminal);
   }
 }
 
 // The same step when the flag buffers are too far from `reward` for 32-bit
-// offsets (80 bytes of arguments).
+// offsets (80 bytes of arguments + the mask job by value: nothing here is
+// preloaded, every wave fetches its arguments).
 __global__ __launch_bounds__(kThreads) void synth_env_far_kernel(
-    const SynthArgs a, uint8_t* is_first, uint8_t* is_last, uint8_t* is_terminal) {
+    const SynthArgs a, uint8_t* is_first, uint8_t* is_last, uint8_t* is_terminal, const SynthMaskJob j) {
   const int64_t e = blockIdx.y;
-  const int32_t n = a.n_turn >> 1, turn = a.n_turn & 1;
-  const int32_t* __restrict__ in = a.counters + turn * 2 * n;
-  int32_t count = in[2 * e];
-  const bool restart = (a.reset && a.reset[e]) || in[2 * e + 1] != 0;
-  const int64_t length = a.episode_len + ((a.env0 + e) % 8) * 13;
-  count = restart ? 0 : count + 1;
-  const bool done = !restart && count >= length;
-  const uint32_t salt = static_cast<uint32_t>((a.env0 + e) * 131 + static_cast<int64_t>(count) * 7);
-  u32x4* out = reinterpret_cast<u32x4*>(a.image + e * a.frame_bytes);
-  const int64_t vecs = a.frame_bytes >> 4;
-  auto word = [salt](int64_t byte0) {
-    const uint32_t x = salt + static_cast<uint32_t>(byte0);
-    return (x & 0xFF) | (((x + 1) & 0xFF) << 8) | (((x + 2) & 0xFF) << 16) | (((x + 3) & 0xFF) << 24);
-  };
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; i < vecs;
-       i += static_cast<int64_t>(gridDim.x) * kThreads)
-    __builtin_nontemporal_store(
-        u32x4{word(i * 16), word(i * 16 + 4), word(i * 16 + 8), word(i * 16 + 12)}, out + i);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    int32_t* next = a.counters + (1 - turn) * 2 * n;
-    next[2 * e] = count;
-    next[2 * e + 1] = done ? 1 : 0;
-    a.reward[e] = restart ? 0.f : static_cast<float>(count % 7);
-    is_first[e] = restart ? 1 : 0;
-    is_last[e] = done ? 1 : 0;
-    is_terminal[e] = done ? 1 : 0;
+  const SynthStep s = synth_step(a, e);
+  synth_frame(a, e, s.count, gridDim.x);
+  if (blockIdx.x == 0) {
+    synth_masked_action(j, a.reset, e);
+    if (threadIdx.x == 0) synth_bookkeeping(a, e, s, is_first, is_last, is_terminal);
   }
 }
 
@@ -2126,44 +2191,102 @@ hipError_t launch_abstract_traj(const float* reward, const float* cont, int64_t 
   return hipGetLastError();
 }
 
+namespace {
+
+bool synth_args(SynthArgs* a, uint8_t* image, float* reward, int64_t n, int64_t frame_bytes, int64_t env0,
+                int64_t episode_len, const uint8_t* reset, int32_t* counters, int turn, dim3* grid) {
+  if (frame_bytes % 16 != 0 || reinterpret_cast<uint64_t>(image) % 16 != 0 || n > (1 << 29) ||
+      frame_bytes > INT32_MAX || env0 > INT32_MAX || episode_len > INT32_MAX)
+    return false;
+  a->counters = counters;
+  a->reset = reset;
+  a->image = image;
+  a->reward = reward;
+  a->off_first = a->off_last = a->off_terminal = 0;
+  a->frame_bytes = static_cast<int32_t>(frame_bytes);
+  a->env0 = static_cast<int32_t>(env0);
+  a->episode_len = static_cast<int32_t>(episode_len);
+  a->n_turn = static_cast<int32_t>(n << 1 | (turn & 1));
+  // A frame over a few workgroups: 64 envs x 4 = one workgroup per CU.
+  const int64_t vecs = frame_bytes >> 4;
+  constexpr int64_t per_env = 4;
+  const uint32_t gx = static_cast<uint32_t>(std::max<int64_t>(1, std::min<int64_t>(per_env, vecs / kThreads)));
+  *grid = dim3(gx, static_cast<uint32_t>(n));
+  return true;
+}
+
+// The flag buffers as 32-bit offsets from `reward`; false when one does not fit.
+bool synth_offsets(const float* reward, const uint8_t* is_first, const uint8_t* is_last,
+                   const uint8_t* is_terminal, int32_t* of, int32_t* ol, int32_t* ot) {
+  const int64_t base = reinterpret_cast<int64_t>(reward);
+  const int64_t f = reinterpret_cast<int64_t>(is_first) - base, l = reinterpret_cast<int64_t>(is_last) - base,
+                t = reinterpret_cast<int64_t>(is_terminal) - base;
+  auto fits = [](int64_t x) { return x >= INT32_MIN && x <= INT32_MAX; };
+  if (!fits(f) || !fits(l) || !fits(t)) return false;
+  *of = static_cast<int32_t>(f);
+  *ol = static_cast<int32_t>(l);
+  *ot = static_cast<int32_t>(t);
+  return true;
+}
+
+int32_t len_turn_word(const SynthArgs& a, int turn) {
+  return static_cast<int32_t>(static_cast<uint32_t>(a.episode_len) | (static_cast<uint32_t>(turn & 1) << 31));
+}
+
+}  // namespace
+
 hipError_t launch_synth_env(uint8_t* image, float* reward, uint8_t* is_first, uint8_t* is_last,
                             uint8_t* is_terminal, int64_t n, int64_t frame_bytes, int64_t env0,
                             int64_t episode_len, const uint8_t* reset, int32_t* counters, int turn,
                             hipStream_t stream) {
   if (n <= 0) return hipSuccess;
-  if (frame_bytes % 16 != 0 || reinterpret_cast<uint64_t>(image) % 16 != 0 || n > (1 << 29) ||
-      frame_bytes > INT32_MAX || env0 > INT32_MAX || episode_len > INT32_MAX)
-    return hipErrorInvalidValue;
   SynthArgs a;
-  a.counters = counters;
-  a.reset = reset;
-  a.image = image;
-  a.reward = reward;
-  a.frame_bytes = static_cast<int32_t>(frame_bytes);
-  a.env0 = static_cast<int32_t>(env0);
-  a.episode_len = static_cast<int32_t>(episode_len);
-  a.n_turn = static_cast<int32_t>(n << 1 | (turn & 1));
-  // A frame over a few workgroups: 64 envs x 4 = one workgroup per CU.
-  const int64_t vecs = frame_bytes >> 4;
-  constexpr int64_t per_env = 4;
-  const uint32_t gx = static_cast<uint32_t>(std::max<int64_t>(1, std::min<int64_t>(per_env, vecs / kThreads)));
-  const dim3 grid(gx, static_cast<uint32_t>(n));
-  const int64_t base = reinterpret_cast<int64_t>(reward);
-  const int64_t of = reinterpret_cast<int64_t>(is_first) - base, ol = reinterpret_cast<int64_t>(is_last) - base,
-                ot = reinterpret_cast<int64_t>(is_terminal) - base;
-  auto fits = [](int64_t x) { return x >= INT32_MIN && x <= INT32_MAX; };
-  if (fits(of) && fits(ol) && fits(ot)) {
-    a.off_first = static_cast<int32_t>(of);
-    a.off_last = static_cast<int32_t>(ol);
-    a.off_terminal = static_cast<int32_t>(ot);
+  dim3 grid;
+  if (!synth_args(&a, image, reward, n, frame_bytes, env0, episode_len, reset, counters, turn, &grid))
+    return hipErrorInvalidValue;
+  if (synth_offsets(reward, is_first, is_last, is_terminal, &a.off_first, &a.off_last, &a.off_terminal)) {
     hipLaunchKernelGGL(synth_env_kernel, grid, dim3(kThreads), 0, stream, a.counters, a.reset, a.image,
                        a.reward, a.off_first, a.off_last, a.off_terminal, a.frame_bytes, a.env0,
-                       static_cast<int32_t>(static_cast<uint32_t>(a.episode_len) |
-                                            (static_cast<uint32_t>(turn & 1) << 31)));
+                       len_turn_word(a, turn));
   } else {
-    a.off_first = a.off_last = a.off_terminal = 0;
     hipLaunchKernelGGL(synth_env_far_kernel, grid, dim3(kThreads), 0, stream, a, is_first, is_last,
-                       is_terminal);
+                       is_terminal, SynthMaskJob{nullptr, nullptr, 0, 0, 1, 0, 0, 0});
+  }
+  return hipGetLastError();
+}
+
+bool synth_mask_job(void* job, const void* act, void* masked_out, int64_t rowbytes, int dtype,
+                    const float* reward, const uint8_t* is_first, const uint8_t* is_last,
+                    const uint8_t* is_terminal) {
+  SynthMaskJob j{static_cast<const uint8_t*>(act), static_cast<uint8_t*>(masked_out),
+                 static_cast<int32_t>(rowbytes), dtype, std::max(dtype_size(dtype), 1), 0, 0, 0};
+  const bool near = synth_offsets(reward, is_first, is_last, is_terminal, &j.off_first, &j.off_last,
+                                  &j.off_terminal);
+  std::memcpy(job, &j, sizeof(j));
+  return near;
+}
+
+hipError_t launch_synth_env_masked(uint8_t* image, float* reward, uint8_t* is_first, uint8_t* is_last,
+                                   uint8_t* is_terminal, int64_t n, int64_t frame_bytes, int64_t env0,
+                                   int64_t episode_len, const uint8_t* reset, int32_t* counters, int turn,
+                                   const void* job_host, const void* job_dev, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  SynthMaskJob j;
+  std::memcpy(&j, job_host, sizeof(j));
+  if (!j.src || !j.out || !carry_supported(j.rowbytes, j.dtype) || j.elem != dtype_size(j.dtype))
+    return hipErrorInvalidValue;
+  SynthArgs a;
+  dim3 grid;
+  if (!synth_args(&a, image, reward, n, frame_bytes, env0, episode_len, reset, counters, turn, &grid))
+    return hipErrorInvalidValue;
+  if (job_dev) {
+    hipLaunchKernelGGL(synth_env_masked_kernel, grid, dim3(kThreads), 0, stream, a.counters, a.reset, a.image,
+                       a.reward, static_cast<const SynthMaskJob*>(job_dev),
+                       a.frame_bytes | static_cast<int32_t>(grid.x - 1), a.env0,
+                       len_turn_word(a, turn), static_cast<int32_t>(n));
+  } else {
+    hipLaunchKernelGGL(synth_env_far_kernel, grid, dim3(kThreads), 0, stream, a, is_first, is_last,
+                       is_terminal, j);
   }
   return hipGetLastError();
 }

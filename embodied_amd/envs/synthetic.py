@@ -22,6 +22,10 @@ class SyntheticBatchEnv:
     # `reset` beside them (this generator never looks at the action of an env
     # it restarts -- nor at any other): see Driver._step_device_env.
     self.takes_unmasked_actions = bool(takes_unmasked_actions)
+    # The step launch masks the actions itself (base.BatchEnv): `step(acts,
+    # unmasked)` stores unmasked * ~reset into acts' tensors, in one launch with
+    # the frames (emb_synth_env_step_masked).  One action key, as its act_space.
+    self.masks_actions_in_step = True
     self.shape = tuple(shape)
     self.frame_bytes = int(np.prod(shape))
     assert self.frame_bytes % 16 == 0
@@ -75,9 +79,21 @@ class SyntheticBatchEnv:
         'is_terminal': _lib.empty((n,), torch.bool, dev),
     }
 
-  def step(self, acts):
+  def step(self, acts, unmasked=None):
+    """One step of all envs.  `unmasked` (masks_actions_in_step): the policy's
+    raw actions by key -- the launch stores `unmasked[k] * ~acts['reset']` into
+    `acts[k]` (the mask of driver.py:72-75, with the same flags the episode logic
+    restarts on) and the env sees only that product."""
     n, dev = self.n, self.device
     reset = acts['reset']
+    job = None
+    if unmasked is not None:
+      (name, raw), = unmasked.items()
+      out = acts[name]
+      code = _DTYPE_CODE[raw.dtype]
+      assert (raw.dtype == out.dtype and raw.shape == out.shape and raw.shape[0] == n
+              and raw.is_contiguous() and out.is_contiguous() and raw.device == out.device == dev), name
+      job = (raw.data_ptr(), out.data_ptr(), raw.numel() // n * raw.element_size(), code)
     if self.ring:
       turn = self.turn
       obs = dict(self.ring[turn])
@@ -85,10 +101,14 @@ class SyntheticBatchEnv:
       # The Driver passes the previous step's is_last as `reset`: with an output
       # ring the launch's arguments repeat with the ring (and the counters'
       # generation) -- remembered per (turn, generation) while `reset` is the
-      # same tensor object.
+      # same tensor object.  The mask job is new every step (the policy's action
+      # tensor) and is added to the remembered arguments.
       cached = self._calls.get((turn, self.generation))
       if cached is not None and cached[0] is reset:
-        fast.emb_synth_env_step(*cached[1], _lib.raw_stream(dev))
+        if job is None:
+          fast.emb_synth_env_step(*cached[1], _lib.raw_stream(dev))
+        else:
+          fast.emb_synth_env_step_masked(*cached[1], *job, _lib.raw_stream(dev))
         self.generation ^= 1
         return obs
       image, reward, is_first, is_last, is_terminal = self._ring_ptrs[turn]
@@ -100,18 +120,29 @@ class SyntheticBatchEnv:
     if reset_ptr == is_last or reset_ptr == is_first or reset_ptr == is_terminal:
       # `reset` is a flag buffer this very step writes (ring=1: the Driver passes
       # the previous is_last): the workgroups that share an env's frame would
-      # read it before and after workgroup 0's store -- step on a copy.
+      # read it before and after workgroup 0's store -- step on a copy (the mask
+      # job reads the same copy: the flags the env logic uses).
       reset = reset.clone()
       reset_ptr = reset.data_ptr()
       turn = -1                   # (a fresh copy per step: nothing to remember)
     args = (image, reward, is_first, is_last, is_terminal, n, self.frame_bytes, self.env0,
             self.episode_len, reset_ptr, self._counters_ptr, self.generation)
-    fast.emb_synth_env_step(*args, _lib.raw_stream(dev))
+    if job is None:
+      fast.emb_synth_env_step(*args, _lib.raw_stream(dev))
+    else:
+      fast.emb_synth_env_step_masked(*args, *job, _lib.raw_stream(dev))
     if turn >= 0:
       self._calls[(turn, self.generation)] = (reset, args)
     self.generation ^= 1
     return obs
 
+
+_DTYPE_CODE = {
+    torch.uint8: _lib.U8, torch.int8: _lib.I8, torch.int16: _lib.I16,
+    torch.int32: _lib.I32, torch.int64: _lib.I64, torch.float16: _lib.F16,
+    torch.bfloat16: _lib.BF16, torch.float32: _lib.F32,
+    torch.float64: _lib.F64, torch.bool: _lib.BOOL,
+}
 
 _RAMPS = {}
 
@@ -132,6 +163,10 @@ class HostSyntheticEnv:
 
   def __init__(self, env, shape=(84, 84, 4), episode_len=1000, actions=6):
     self.env = env
+    # The step launch masks the actions itself (base.BatchEnv): `step(acts,
+    # unmasked)` stores unmasked * ~reset into acts' tensors, in one launch with
+    # the frames (emb_synth_env_step_masked).  One action key, as its act_space.
+    self.masks_actions_in_step = True
     self.shape = tuple(shape)
     self.frame_bytes = int(np.prod(shape))
     self.length = episode_len + (env % 8) * 13

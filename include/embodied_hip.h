@@ -568,6 +568,24 @@ int32_t emb_synth_env_step(void* image, void* reward, void* is_first, void* is_l
                            void* is_terminal, int64_t n, int64_t frame_bytes, int64_t env0,
                            int64_t episode_len, const void* reset, void* counters,
                            int32_t turn, void* stream);
+/* The same step with the Driver's action mask (driver.py:72-75) inside the
+ * launch: `act` = the policy's raw actions, device (n, row_bytes) of `dtype`
+ * (EMB_U8 ...); the launch also stores act * !reset[e], a real multiply in
+ * `dtype`, to `masked_out` -- the env's input -- and the env uses nothing but
+ * that product.  `reset` must be given (the Driver passes the previous step's
+ * is_last).  Keys: those emb_env_mask_supported accepts (1..256 elements per
+ * row: what a carried publish takes, emb_replay_carry_publish); anything else
+ * is EMB_ERR_INVALID.  No extra launch: with emb_replay_carry_publish an env
+ * step is two dependent launches instead of three.                             */
+int32_t emb_synth_env_step_masked(void* image, void* reward, void* is_first, void* is_last,
+                                  void* is_terminal, int64_t n, int64_t frame_bytes,
+                                  int64_t env0, int64_t episode_len, const void* reset,
+                                  void* counters, int32_t turn, const void* act,
+                                  void* masked_out, int64_t row_bytes, int32_t dtype,
+                                  void* stream);
+/* 1 if an action key of this row size and dtype can be masked inside a device
+ * env's step launch (and carried by the replay), else 0.                        */
+int32_t emb_env_mask_supported(int64_t row_bytes, int32_t dtype);
 
 /* ---- direct xGMI schedule (round 5) ----------------------------------------
  * The two collectives of a train step -- the gradient all-reduce
