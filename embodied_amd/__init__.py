@@ -30,6 +30,8 @@ from . import envs
 from . import utils
 from . import run
 from . import distributed
+from . import normalize
+from .normalize import DeviceNormalize
 from .utils import Counter, LocalClock
 from .distributed import GlobalClock
 # `embodied.clock.*` by name (embodied/core/__init__.py:4-5,11): the two clocks and

@@ -24,6 +24,7 @@ STEPID_BYTES = 20
 U8, I8, I16, I32, I64, F16, BF16, F32, F64, BOOL = range(10)
 LAYOUT_SAME, LAYOUT_CHANNELS_FIRST = 0, 1
 MODES = {'train': 0, 'report': 1, 'eval': 2}
+NORM_MEANSTD, NORM_PERC = 1, 2
 
 
 class EmbError(RuntimeError):
@@ -65,6 +66,13 @@ class ObsSpec(C.Structure):
   _fields_ = [
       ('pixels', C.c_int64), ('channels', C.c_int64), ('layout', C.c_int32),
       ('out_dtype', C.c_int32), ('scale', C.c_float), ('offset', C.c_float)]
+
+
+class NormalizeConfig(C.Structure):
+  """emb_normalize_config_t: the hyper-parameters of emb_normalize."""
+  _fields_ = [
+      ('impl', C.c_int32), ('debias', C.c_int32), ('rate', C.c_double), ('limit', C.c_double),
+      ('perclo', C.c_double), ('perchi', C.c_double)]
 
 
 class SelectorCallbacks(C.Structure):
@@ -187,6 +195,8 @@ SIGNATURES = {
     'emb_replay_settle': [p],
     'emb_scan_director': [p, p, p, i64, i64, f32, f32, p, p],
     'emb_abstract_traj': [p, p, i64, i64, i32, p, p, p],
+    'emb_normalize': [p, p, i64, p, i32, p, p, p],
+    'emb_normalize_launches': [p],
     'emb_synth_env_step': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p],
     'emb_synth_env_step_masked': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p, p, i64, i32, p],
     'emb_env_mask_supported': [i64, i32],
@@ -316,7 +326,7 @@ class _FastApi:
       'emb_comm_exchange': 'ints', 'emb_comm_wait': 'ints',
       'emb_direct_exchange': 'ints', 'emb_direct_wait': 'ints',
       'emb_comm_exchange_gather': 'ints', 'emb_direct_exchange_gather': 'ints',
-      'emb_copy_bytes': 'ints', 'emb_mask_actions_notify': 'ints',
+      'emb_copy_bytes': 'ints', 'emb_mask_actions_notify': 'ints', 'emb_normalize': 'ints',
   }
 
   def __init__(self, module):

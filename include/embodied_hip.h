@@ -495,6 +495,44 @@ int32_t emb_scan_director(const void* rew, const void* cont, const void* value, 
 int32_t emb_abstract_traj(const void* reward, const void* cont, int64_t T, int64_t B, int32_t k,
                           void* reward_out, void* cont_out, void* stream);
 
+/* ---- running return normaliser, float32 on device -------------------------
+ * The reference's Normalize (embodied/jax/utils.py:16-91: DreamerV3's retnorm /
+ * valnorm / advnorm, the advantage normaliser of the PPO loss) for ONE replica,
+ * as one kernel launch of one workgroup.  `state` is five float32 words of
+ * DEVICE memory that the caller owns and zeroes once:
+ *   [0] mean | lo   [1] sqrs | hi   [2] corr   [3] offset   [4] scale
+ * update != 0: the running statistics take one EMA step
+ * (1 - rate) * var + rate * value from x[0 .. n) (contiguous float32 on device):
+ *   EMB_NORM_MEANSTD  value = mean(x), mean(x * x)   (accumulated in float64)
+ *   EMB_NORM_PERC     value = the perclo-th and perchi-th percentile with numpy's
+ *                     "linear" method: pos = q / 100 * (n - 1) in double, the
+ *                     two neighbouring order statistics selected exactly
+ *                     (radix select), a + (b - a) * frac
+ * and, with `debias`, corr moves towards 1.  Then, always (utils.py:59-74):
+ *   corr = debias ? 1 / max(rate, state[2]) : 1
+ *   MEANSTD  offset = mean * corr,  scale = max(limit, sqrt(relu(sqrs * corr - offset^2)))
+ *   PERC     offset = lo * corr,    scale = max(limit, hi * corr - offset)
+ * out != NULL: the same launch also writes
+ *   out[i] = (x[i] - (sub ? sub[i] : offset)) / scale     (out may be x)
+ * Nothing returns to the host: no synchronisation, no allocation.  Up to 16384
+ * values stay in LDS; more are re-read from global memory by the same launch.
+ * EMB_ERR_INVALID before any launch: a NULL config / state (or x with n > 0),
+ * n < 0, an unknown impl, rate outside [0, 1], a percentile outside [0, 100],
+ * update with n = 0, sub without out.                                          */
+#define EMB_NORM_MEANSTD 1
+#define EMB_NORM_PERC 2
+typedef struct emb_normalize_config {
+  int32_t impl;      /* EMB_NORM_MEANSTD | EMB_NORM_PERC                        */
+  int32_t debias;
+  double rate, limit;   /* as given: 1 - rate is formed in double, then each is rounded to float32 */
+  double perclo, perchi;
+} emb_normalize_config_t;
+int32_t emb_normalize(const emb_normalize_config_t* config, const void* x, int64_t n, void* state,
+                      int32_t update, const void* sub, void* out, void* stream);
+/* Kernel launches emb_normalize has issued in this process, counted where the
+ * kernel is launched.                                                         */
+int32_t emb_normalize_launches(int64_t* count);
+
 /* ----------------------------------------------------------- collectives --
  * The two exchange steps of the sharded path on RCCL directly (xGMI inside one
  * node), for hosts that do not go through torch.distributed:
