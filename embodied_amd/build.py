@@ -18,8 +18,8 @@ HERE = pathlib.Path(__file__).resolve().parent
 CSRC = HERE / 'csrc'
 OUT = HERE / 'libembodied_hip.so'
 OBJ = HERE / 'build'
-SOURCES = ['kernels.hip', 'direct_comm.hip', 'normalize.hip', 'replay_abi.cpp', 'index_abi.cpp', 'kernels_abi.cpp', 'env_abi.cpp',
-           'comm_abi.cpp', 'normalize_abi.cpp']
+SOURCES = ['movers.hip', 'step.hip', 'scans.hip', 'synth_env.hip', 'direct_comm.hip', 'normalize.hip', 'replay_abi.cpp',
+           'index_abi.cpp', 'kernels_abi.cpp', 'env_abi.cpp', 'comm_abi.cpp', 'normalize_abi.cpp']
 ARCH = 'gfx950'
 # CPython call shim for the hottest entry points (csrc/fastcall.c): plain C,
 # links against nothing; the package falls back to ctypes without it.
@@ -58,6 +58,23 @@ def scratch_users(remarks):
   return out
 
 
+def hip_flags():
+  """hipcc flags of every translation unit (tools/kernel_table.py compiles with the same)."""
+  flags = [f'--offload-arch={ARCH}', '-O3', '-std=c++17', '-fPIC', '-Wall', '-fvisibility=hidden',
+           '-fvisibility-inlines-hidden', '-ffunction-sections',
+           '-Wno-unused-function', '-Wno-pass-failed', '-x', 'hip']
+  # Kernel-argument preload (gfx940+): the first 16 dwords of a kernel's
+  # arguments arrive in SGPRs with the wave instead of being fetched by every
+  # wave's first s_load.  With host-resident kernel arguments that fetch is a
+  # PCIe round trip per wave: preloading takes 1-2 us off every small kernel and
+  # off the movers that read their plan through one pointer argument.
+  # EMB_KERNARG_PRELOAD=0 builds without it.
+  preload = os.environ.get('EMB_KERNARG_PRELOAD', '16')
+  if preload not in ('', '0'):
+    flags += ['-mllvm', f'-amdgpu-kernarg-preload-count={int(preload)}']
+  return flags
+
+
 def stale():
   if not OUT.exists() or not FASTCALL.exists():
     return True
@@ -76,18 +93,7 @@ def build(force=False, verbose=True):
   fcntl.flock(lock, fcntl.LOCK_EX)
   if not force and not stale():
     return OUT
-  flags = [f'--offload-arch={ARCH}', '-O3', '-std=c++17', '-fPIC', '-Wall', '-fvisibility=hidden',
-           '-fvisibility-inlines-hidden', '-ffunction-sections',
-           '-Wno-unused-function', '-Wno-pass-failed', '-x', 'hip']
-  # Kernel-argument preload (gfx940+): the first 16 dwords of a kernel's
-  # arguments arrive in SGPRs with the wave instead of being fetched by every
-  # wave's first s_load.  With host-resident kernel arguments that fetch is a
-  # PCIe round trip per wave: preloading takes 1-2 us off every small kernel and
-  # off the movers that read their plan through one pointer argument.
-  # EMB_KERNARG_PRELOAD=0 builds without it.
-  preload = os.environ.get('EMB_KERNARG_PRELOAD', '16')
-  if preload not in ('', '0'):
-    flags += ['-mllvm', f'-amdgpu-kernarg-preload-count={int(preload)}']
+  flags = hip_flags()
 
   def compile_one(name):
     obj = OBJ / (name + '.o')

@@ -1,4 +1,5 @@
-// Launchers for the gfx950 kernels in kernels.hip (host-callable, no torch).
+// Launchers for the gfx950 kernels in movers.hip, step.hip, scans.hip and
+// synth_env.hip (host-callable, no torch).
 #pragma once
 
 #include <hip/hip_runtime.h>

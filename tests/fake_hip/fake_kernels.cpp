@@ -6,7 +6,8 @@
 // them: a row index the host core got wrong is an out-of-bounds access ASan
 // sees, a pool access outside the replay's locks is a race TSan sees.
 // The product never links this file: libembodied_hip.so is built from
-// csrc/kernels.hip and fails to load without the HIP runtime.
+// csrc/movers.hip, step.hip, scans.hip and synth_env.hip and fails to load
+// without the HIP runtime.
 #include "kernels.h"
 
 #include <cstring>

@@ -1177,7 +1177,7 @@ def test_save_load_with_prioritized_selector(emb, tmp_path):
     (8, 9, (2, 40)),            # windows of 2-3 chunks: NOT span-shaped, falls back to row tables
 ])
 def test_span_mover_several_wide_keys_match_oracle(emb, chunksize, L, batches):
-  """The persistent span mover (kernels.hip move_wide_spans: sample, windowing
+  """The persistent span mover (movers.hip move_wide_spans: sample, windowing
   and write-back of keys with >= 2 KB rows) against the oracle: three wide keys
   of different row sizes next to the narrow ones, tiles that straddle the run
   split and the end of a sequence, gather and scatter directions."""

@@ -1,4 +1,4 @@
-// Shapes of the obs-stack + early-insert launch (kernels.hip obs_stack_insert_kernel,
+// Shapes of the obs-stack + early-insert launch (step.hip obs_stack_insert_kernel,
 // bf16 channels-first, C = 4) inside the chain it runs in: producer (frames of the
 // step, like the synthetic env) -> insert -> producer -> ...  on one stream, every
 // launch dependent on the one before.  Prints the chain's period per pair and the
