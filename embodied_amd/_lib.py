@@ -197,6 +197,8 @@ SIGNATURES = {
     'emb_abstract_traj': [p, p, i64, i64, i32, p, p, p],
     'emb_normalize': [p, p, i64, p, i32, p, p, p],
     'emb_normalize_launches': [p],
+    'emb_ppo_targets': [p, p, p, p, p, p, i64, i64, f32, f32, f32, i32, p, p, p, p, p, p, p],
+    'emb_ppo_targets_launches': [p],
     'emb_synth_env_step': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p],
     'emb_synth_env_step_masked': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p, p, i64, i32, p],
     'emb_env_mask_supported': [i64, i32],
@@ -327,6 +329,7 @@ class _FastApi:
       'emb_direct_exchange': 'ints', 'emb_direct_wait': 'ints',
       'emb_comm_exchange_gather': 'ints', 'emb_direct_exchange_gather': 'ints',
       'emb_copy_bytes': 'ints', 'emb_mask_actions_notify': 'ints', 'emb_normalize': 'ints',
+      'emb_ppo_targets': 'ppo_targets',
   }
 
   def __init__(self, module):

@@ -8,11 +8,12 @@
  * exported functions through their addresses (taken from the ctypes handle),
  * converting arguments itself: Python int / None / objects with the buffer
  * protocol (ctypes arrays) -> 64-bit integer registers, Python float -> float.
- * It links against nothing but libpython and knows three call shapes:
+ * It links against nothing but libpython and knows four call shapes:
  *
  *   ints(addr, a0 .. aN)            every argument is a pointer or an integer
  *   obs_stack(addr, 11 args)        emb_obs_stack  (two floats at 7, 8)
  *   scan(addr, 10 or 11 args)       emb_scan_gae / emb_scan_lambda (floats at 6, 7)
+ *   ppo_targets(addr, 19 args)      emb_ppo_targets (floats at 8, 9, 10)
  *
  * On x86-64 SysV an int32 parameter reads the low half of the 64-bit register
  * or stack slot it is passed in, so integer-class arguments are all passed as
@@ -161,6 +162,33 @@ static PyObject* call_scan(PyObject* self, PyObject* const* args, Py_ssize_t nar
   else
     status = ((int32_t(*)(u64, u64, u64, u64, u64, u64, float, float, u64, u64))fn)(
         a[1], a[2], a[3], a[4], a[5], a[6], f[0], f[1], a[9], a[10]);
+  Py_END_ALLOW_THREADS
+  return PyLong_FromLong(status);
+}
+
+/* emb_ppo_targets(valnorm, advnorm, rew, pred, last, term, B, T, live_scale, lam, tarclip, update,
+ *                 adv, tar, tar_normed, adv_normed, valnorm_state, advnorm_state, stream)          19 */
+static PyObject* call_ppo_targets(PyObject* self, PyObject* const* args, Py_ssize_t nargs) {
+  if (nargs != 20) {
+    PyErr_SetString(PyExc_TypeError, "fastcall.ppo_targets(addr, 19 arguments)");
+    return NULL;
+  }
+  u64 a[20] = {0};
+  float f[3];
+  for (Py_ssize_t i = 0; i < nargs; ++i) {
+    if (i >= 9 && i <= 11) {
+      if (as_float(args[i], &f[i - 9]) < 0) return NULL;
+    } else if (as_u64(args[i], &a[i]) < 0) {
+      return NULL;
+    }
+  }
+  void* fn = (void*)(uintptr_t)a[0];
+  int32_t status;
+  Py_BEGIN_ALLOW_THREADS
+  status = ((int32_t(*)(u64, u64, u64, u64, u64, u64, u64, u64, float, float, float, u64, u64, u64, u64, u64,
+                        u64, u64, u64))fn)(
+      a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], f[0], f[1], f[2], a[12], a[13], a[14], a[15], a[16],
+      a[17], a[18], a[19]);
   Py_END_ALLOW_THREADS
   return PyLong_FromLong(status);
 }
@@ -517,6 +545,8 @@ static PyMethodDef methods[] = {
      "obs_stack(addr, *11 args) -> status"},
     {"scan", (PyCFunction)(void (*)(void))call_scan, METH_FASTCALL,
      "scan(addr, *10 or 11 args) -> status"},
+    {"ppo_targets", (PyCFunction)(void (*)(void))call_ppo_targets, METH_FASTCALL,
+     "ppo_targets(addr, *19 args) -> status"},
     {"columns", (PyCFunction)(void (*)(void))call_columns, METH_FASTCALL,
      "columns(steps, plan, out, tensor_type, device) -> None | positions for the slow path"},
     {"stage_plan", (PyCFunction)(void (*)(void))call_stage_plan, METH_FASTCALL,

@@ -5,20 +5,16 @@
 //
 // Up to kNormLdsMax values keep their order-preserving integer keys in LDS; more
 // values are re-read from global memory by every pass of the same kernel.
-#include "normalize.h"
+#include "normalize_device.h"   // (float32 operations one by one: fp contract off)
 
 #include <atomic>
 #include <cmath>
 
-// The reference runs float32 operations one by one; a fused multiply-add would
-// round once where it rounds twice.
-#pragma clang fp contract(off)
-
 namespace emb {
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kWaves = kNormThreads / kWave;
+constexpr int kWave = kNormWave;
+constexpr int kWaves = kNormWaves;
 constexpr int kBins = 2048;      // digits of 11, 11 and 10 bits, most significant first
 
 // float32 -> uint32 with the same order (-0.0 sorts just below +0.0).
@@ -76,10 +72,6 @@ __device__ __forceinline__ void hist_add(uint32_t* hist, bool active, uint32_t b
   }
 }
 
-__device__ __forceinline__ float ema(float keep, float var, float rate, float value) {
-  return keep * var + rate * value;
-}
-
 template <bool kLds>
 __global__ __launch_bounds__(kNormThreads) void normalize_kernel(
     const float* x, const float* sub, float* out, float* state, uint32_t n, uint32_t flags,
@@ -114,20 +106,9 @@ __global__ __launch_bounds__(kNormThreads) void normalize_kernel(
       s += static_cast<double>(v);
       s2 += static_cast<double>(v * v);
     }
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-      s += __shfl_xor(s, o);
-      s2 += __shfl_xor(s2, o);
-    }
-    if (lane == 0) {
-      sums[wave][0] = s;
-      sums[wave][1] = s2;
-    }
-    __syncthreads();
-    s = 0.0, s2 = 0.0;
-    for (int w = 0; w < kWaves; ++w) {
-      s += sums[w][0];
-      s2 += sums[w][1];
-    }
+    double both[2] = {s, s2};
+    norm_block_sum(both, sums);
+    s = both[0], s2 = both[1];
     new0 = static_cast<float>(s / static_cast<double>(n));
     new1 = static_cast<float>(s2 / static_cast<double>(n));
   }
@@ -211,32 +192,9 @@ __global__ __launch_bounds__(kNormThreads) void normalize_kernel(
     new1 = after1 == prefix1 ? a1 : a1 + (b1 - a1) * frac_hi;
   }
 
-  if (update) {
-    v0 = ema(keep, v0, rate, new0);
-    v1 = ema(keep, v1, rate, new1);
-    if (debias) vc = ema(keep, vc, rate, 1.0f);
-  }
-  const float corr = debias ? 1.0f / fmaxf(rate, vc) : 1.0f;
-  float offset, scale;
-  if (impl == kNormMeanStd) {
-    const float mean = v0 * corr;
-    const float var = v1 * corr - mean * mean;
-    offset = mean;
-    scale = fmaxf(limit, sqrtf(fmaxf(0.f, var)));
-  } else {
-    const float lo = v0 * corr, hi = v1 * corr;
-    offset = lo;
-    scale = fmaxf(limit, hi - lo);
-  }
-  if (tid == 0) {
-    if (update) {
-      state[0] = v0;
-      state[1] = v1;
-      if (debias) state[2] = vc;
-    }
-    state[3] = offset;
-    state[4] = scale;
-  }
+  const NormWords w = norm_step(v0, v1, vc, new0, new1, impl, update, debias, NormParams{keep, rate, limit});
+  const float offset = w.offset, scale = w.scale;
+  if (tid == 0) norm_store(state, w, update, debias);
 
   if (out) {       // out may be x: every element is read and written by the same lane
     const bool wide = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) |

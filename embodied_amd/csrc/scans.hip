@@ -1,4 +1,4 @@
-#include "device_util.h"
+#include "scan_segment.h"
 
 #include <algorithm>
 #include <cstring>
@@ -10,66 +10,10 @@ namespace {
 // ------------------------------------------------------------ return scans --
 //
 // y_t = a_t + b_t * y_{t+1}.  A segment of W lanes owns one row; lane = time
-// step.  Reverse inclusive Kogge-Stone over the affine maps
-// (a1,b1) o (a2,b2) = (a1 + b1*a2, b1*b2) with __shfl_down inside the segment,
-// rows longer than W are walked right-to-left in W-wide pieces with the
-// running y carried in a register.  Episode boundaries need no flags: b_t = 0.
-
-// Composite map of lanes [sl, W) of a segment: returns (A, B) with
-// y_sl = A + B * y_{segment end + 1}.
-template <int W>
-__device__ __forceinline__ void affine_suffix(float& a, float& b, int sl) {
-#pragma unroll
-  for (int off = 1; off < W; off <<= 1) {
-    const float ap = __shfl_down(a, off, W);
-    const float bp = __shfl_down(b, off, W);
-    if (sl + off < W) {
-      a = fmaf(b, ap, a);
-      b = b * bp;
-    }
-  }
-}
-
-// Four consecutive elements of a row at once.  Rows start wherever b*T puts
-// them, so the vector types promise dword (floats) resp. byte (flags)
-// alignment only; gfx950 serves such global loads in one instruction.
-typedef float F4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef uint8_t B4 __attribute__((ext_vector_type(4), aligned(1)));
-// (A branch-free form -- the short lane reads the four elements that END at
-// its last one and shifts them down -- measured slower: 15.6 us against 13.4 at
-// (65 536, 64), no gain at small sizes.)
-__device__ __forceinline__ void load4(const float* p, int valid, float* out) {
-  if (valid >= 4) {
-    const F4 x = gload<F4>(p);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = x[k];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = k < valid ? gload<float>(p + k) : 0.f;
-  }
-}
-__device__ __forceinline__ void load4(const uint8_t* p, int valid, uint8_t* out) {
-  if (valid >= 4) {
-    const B4 x = gload<B4>(p);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = x[k];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = k < valid ? gload<uint8_t>(p + k) : uint8_t{0};
-  }
-}
-__device__ __forceinline__ void store4(float* p, int valid, const float* y) {
-  if (valid >= 4) {
-    F4 x;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) x[k] = y[k];
-    gstore<F4>(p, x);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (k < valid) gstore<float>(p + k, y[k]);
-  }
-}
+// step (scan_segment.h: the Kogge-Stone over the affine maps, the four-element
+// loads and stores, the four-steps-per-lane piece); rows longer than W are
+// walked right-to-left in W-wide pieces with the running y carried in a
+// register.
 
 // What differs between the scans: how (a_t, b_t) are formed from the inputs,
 // the seed y_n, and what is stored.
@@ -138,43 +82,7 @@ struct GaeOp : std::conditional_t<kGrouped, Groups, NoGroups> {   // ppo/agent.p
     const int64_t i = b * T + t0;
     int64_t ir, il;
     where(b, t0, ir, il);
-    // val[t0 .. t0+valid]: one more than the elements, the last one's successor
-    // (it exists: t0 + valid <= T - 1).
-    float v[5], r[4];
-    uint8_t tm[4], ls[4];
-    float after;
-    if (valid >= 4) {
-      // the usual lane: all five loads issued back to back, one wait
-      const F4 v4 = gload<F4>(val + i);
-      after = gload<float>(val + i + 4);
-      const F4 r4 = gload<F4>(rew + ir + 1);
-      const B4 t4 = gload<B4>(term + il + 1);
-      const B4 l4 = gload<B4>(last + il + 1);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        v[k] = v4[k];
-        r[k] = r4[k];
-        tm[k] = t4[k];
-        ls[k] = l4[k];
-      }
-    } else {
-      load4(val + i, valid, v);
-      after = gload<float>(val + i + valid);
-      load4(rew + ir + 1, valid, r);
-      load4(term + il + 1, valid, tm);
-      load4(last + il + 1, valid, ls);
-    }
-    v[4] = after;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float next = k + 1 == valid ? after : v[k + 1];
-      const bool t_ = tm[k] != 0;
-      const float live = t_ ? 0.f : live_scale;
-      const float cont = (t_ || ls[k] != 0) ? 0.f : lam;
-      keep[k] = v[k];
-      a[k] = r[k] + live * next - v[k];
-      bc[k] = live * cont;
-    }
+    gae_coef4(val, i, rew, ir, term, last, il, valid, live_scale, lam, [](float v) { return v; }, a, bc, keep);
   }
   __device__ void store4(int64_t b, int t0, int valid, const float* y, const float* keep) const {
     float z[4];
@@ -283,30 +191,8 @@ __device__ __forceinline__ void scan_rows4_body(const Op& op, uint32_t block) {
   const int t0 = 4 * sl;
   const bool row_ok = b < B;
   const int valid = row_ok ? (n - t0 >= 4 ? 4 : (n - t0 > 0 ? n - t0 : 0)) : 0;
-  float a[4] = {0.f, 0.f, 0.f, 0.f}, bc[4] = {1.f, 1.f, 1.f, 1.f}, keep[4] = {0.f, 0.f, 0.f, 0.f};
-  if (valid > 0) op.coef4(b, t0, valid, a, bc, keep);
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (k >= valid) {            // (0, 1) = identity map right of the row's end
-      a[k] = 0.f;
-      bc[k] = 1.f;
-    }
-  // this lane's four elements as one map, then the maps of the lanes to the right
-  float A = a[3], Bm = bc[3];
-#pragma unroll
-  for (int k = 2; k >= 0; --k) {
-    A = fmaf(bc[k], A, a[k]);
-    Bm = bc[k] * Bm;
-  }
-  affine_suffix<W>(A, Bm, sl);
-  const float seed = row_ok ? op.seed(b) : 0.f;
-  const float first = fmaf(Bm, seed, A);               // y at t0
-  float carry = __shfl_down(first, 1, W);              // y at t0 + 4 = the next lane's first
-  if (sl == W - 1) carry = seed;
-  float y[4];
-  y[3] = fmaf(bc[3], carry, a[3]);
-#pragma unroll
-  for (int k = 2; k >= 0; --k) y[k] = fmaf(bc[k], y[k + 1], a[k]);
+  float y[4], keep[4] = {0.f, 0.f, 0.f, 0.f};
+  scan_piece4<W>(op, b, t0, valid, sl, [&] { return row_ok ? op.seed(b) : 0.f; }, y, keep);
   if (valid > 0) op.store4(b, t0, valid, y, keep);
 }
 template <int W, typename Op, typename... Args>

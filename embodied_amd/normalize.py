@@ -45,6 +45,7 @@ class DeviceNormalize:
     self.perclo, self.perchi, self.debias = perclo, perchi, debias
     self._buffer = None
     self._pending = {}          # a checkpoint loaded before the device is known
+    self._current = False       # words 3-4 hold (offset, scale) of words 0-2: `latest`
     if impl != 'none':
       self._config = _lib.NormalizeConfig(
           _IMPLS[impl], int(bool(debias)), float(rate), float(limit), float(perclo), float(perchi))
@@ -87,6 +88,7 @@ class DeviceNormalize:
         self._config_ptr, None if x is None else x.data_ptr(), 0 if x is None else x.numel(),
         self._ptr, int(update), None if sub is None else sub.data_ptr(),
         None if out is None else out.data_ptr(), _lib.raw_stream(self._buffer.device))
+    self._current = True
 
   # -------------------------------------------------------------- interface --
 
@@ -113,6 +115,24 @@ class DeviceNormalize:
     self._state()
     self._launch(None, False)
     return self._stats
+
+  def latest(self):
+    """`stats()` without its launch where the last launch on this object already
+    left (offset, scale) of the present statistics in the state buffer (every
+    launch does; a loaded checkpoint or a fresh object does not: then `stats()`)."""
+    if self.impl == 'none' or not self._current:
+      return self.stats()
+    return self._stats
+
+  def fused(self, device):
+    """(config address, state address) for a launch that runs this normaliser's
+    step inside another kernel (`scans.ppo_targets`): the kernel leaves the state
+    words as `emb_normalize` would, (offset, scale) included."""
+    self._state(device)
+    if self._buffer.device != device:
+      raise ValueError(f'DeviceNormalize: the statistics are on {self._buffer.device}, the launch on {device}')
+    self._current = True
+    return self._config_ptr, self._ptr
 
   def normalize(self, x, sub=None, out=None, update=True):
     """(x - offset) / scale, or (x - sub) / scale with `sub` (DreamerV3:
@@ -168,6 +188,7 @@ class DeviceNormalize:
         return
       self._state(device)
     words = [values.get(name, 0.0) for name in names]
+    self._current = False
     if all(torch.is_tensor(v) for v in words):      # device to device, in stream order
       self._buffer[:3].copy_(torch.stack([v.detach().to(self._buffer.device, torch.float32).reshape(()) for v in words]))
     else:

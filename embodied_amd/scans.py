@@ -1,9 +1,11 @@
 """Return scans on device (float32): GAE (ppo/agent.py:188-201), lambda-return
 (dreamerv3/agent.py:482-490) and the Director critic target
-(director/agent.py:430-445), each one kernel launch.
+(director/agent.py:430-445), each one kernel launch; and the PPO targets
+(ppo/agent.py:188-210: GAE with both return normalisers) as one launch.
 
 Inputs are torch CUDA tensors; bool flags may be torch.bool or uint8.
 """
+import collections
 import os
 import sys
 
@@ -130,6 +132,111 @@ def gae(rew, val, last, term, hor=200, lam=0.8, out=None):
       _round32(1 - 1 / hor), _round32(lam), adv.data_ptr(),
       tar.data_ptr(), _stream(rew))
   return adv, tar
+
+
+class PpoTargets(collections.namedtuple('PpoTargets', 'adv tar tar_normed adv_normed')):
+  """What the top of ppo_loss hands on: adv, tar (B,T-1), the clipped normalised
+  target padded to (B,T), the normalised advantage (B,T-1)."""
+
+
+# B * T up to which `ppo_targets(fused=None)` takes the one-workgroup kernel:
+# the largest size of profiles/ppo_targets_bench.txt at which it still beat the
+# composed path (16 384 values: 19.8 us against 35.3 at (1024, 16), 17.5 against
+# 41.1 at (16, 1024); 7.0 against 40.1 at PPO's (16, 64)).  The next measured size,
+# (4096, 64), loses 272 us to 132: between the two nothing was measured.
+PPO_TARGETS_FUSED_MAX = 16384
+
+
+def ppo_targets_launches():
+  """Kernel launches `emb_ppo_targets` has issued in this process."""
+  import ctypes as C
+  count = C.c_int64(0)
+  api.emb_ppo_targets_launches(C.byref(count))
+  return count.value
+
+
+def _ppo_targets_path(fused, valnorm, advnorm, B, T):
+  """True: the kernel, False: the composed path (`ppo_targets` says when)."""
+  meanstd = valnorm.impl == 'meanstd' and advnorm.impl == 'meanstd'
+  if fused and not meanstd:
+    raise ValueError(
+        f"ppo_targets(fused=True): the kernel runs 'meanstd' normalisers, got valnorm "
+        f"'{valnorm.impl}' and advnorm '{advnorm.impl}' (fused=None or False composes them)")
+  if fused is None:
+    return meanstd and B * T <= PPO_TARGETS_FUSED_MAX
+  return bool(fused)
+
+
+def ppo_targets(rew, pred, last, term, valnorm, advnorm, hor=200, lam=0.8, tarclip=10.0,
+                update=True, out=None, fused=None):
+  """The top of ppo_loss (ppo/agent.py:188-210): val = pred * vscale + voffset
+  with valnorm's statistics before the step, GAE, `valnorm(tar, update)`, the
+  target normalised, clipped to +-tarclip (None / 0: no clip) and padded with a
+  zero column, `advnorm(adv, update)`, the advantage normalised.
+  rew, pred (B,T) f32; last, term (B,T) bool; valnorm, advnorm: `DeviceNormalize`
+  -> PpoTargets(adv, tar (B,T-1), tar_normed (B,T), adv_normed (B,T-1)).
+
+  Afterwards both normalisers hold what `valnorm.stats()`, `valnorm(tar)` and
+  `advnorm(adv)` would have left.  Two paths compute it:
+    composed  torch's multiply-add, `gae`, `valnorm.normalize`, torch's clip and
+              pad, `advnorm.normalize`: every impl, every size.  The definition.
+    fused     ONE launch of one workgroup (`emb_ppo_targets`): both impls 'meanstd'.
+  `fused=None` takes the kernel where it is the faster one (both 'meanstd',
+  B * T <= PPO_TARGETS_FUSED_MAX), True / False force a path (True raises unless
+  both are 'meanstd').  `out=(adv, tar, tar_normed, adv_normed)`: the caller's
+  contiguous float32 tensors; without it one allocation holds all four."""
+  dev = _device(rew, pred, last, term)
+  rew, pred = _f32(rew, dev), _f32(pred, dev)
+  last, term = _flag(last, dev), _flag(term, dev)
+  B, T = rew.shape
+  assert pred.shape == last.shape == term.shape == (B, T)
+  fused = _ppo_targets_path(fused, valnorm, advnorm, B, T)
+  n = max(T - 1, 0)
+  shapes = ((B, n), (B, n), (B, T), (B, n))
+  if out is not None:
+    results = tuple(out)
+    if len(results) != 4:
+      raise ValueError('ppo_targets(out=): needs (adv, tar, tar_normed, adv_normed)')
+    for result, shape in zip(results, shapes):
+      if torch.is_tensor(result) and result.__dict__.get('_emb_ppo_out') == (shape, dev):
+        continue          # (marked like gae's: an agent hands the same result tensors in again)
+      if (not torch.is_tensor(result) or result.dtype != torch.float32 or tuple(result.shape) != shape
+          or result.device != dev or not result.is_contiguous()):
+        raise ValueError(
+            f'ppo_targets(out=): needs contiguous float32 tensors of shapes {shapes} on {dev}')
+      result._emb_ppo_out = (shape, dev)
+  else:
+    # one allocation; every part starts on a 16-byte boundary (the kernel's wide path)
+    sizes = [(rows * cols + 3) // 4 * 4 for rows, cols in shapes]
+    flat = _lib.empty((sum(sizes),), torch.float32, dev)
+    results, start = [], 0
+    for size, (rows, cols) in zip(sizes, shapes):
+      results.append(flat[start:start + rows * cols].view(rows, cols))
+      start += size
+    results = tuple(results)
+  adv, tar, tar_normed, adv_normed = results
+  if B == 0 or T < 2:
+    tar_normed.zero_()
+    return PpoTargets(adv, tar, tar_normed, adv_normed)
+  if fused:
+    vconfig, vstate = valnorm.fused(dev)
+    aconfig, astate = advnorm.fused(dev)
+    fast.emb_ppo_targets(
+        vconfig, aconfig, rew.data_ptr(), pred.data_ptr(), last.data_ptr(), term.data_ptr(), B, T,
+        _round32(1 - 1 / hor), _round32(lam), _round32(tarclip) if tarclip else 0.0, int(bool(update)),
+        adv.data_ptr(), tar.data_ptr(), tar_normed.data_ptr(), adv_normed.data_ptr(), vstate, astate,
+        _stream(rew))
+    return PpoTargets(adv, tar, tar_normed, adv_normed)
+  voffset, vscale = valnorm.latest()
+  val = pred * vscale + voffset
+  gae(rew, val, last, term, hor, lam, out=(adv, tar))
+  normed = tar_normed[:, :-1]
+  normed.copy_(valnorm.normalize(tar, update=update))
+  if tarclip:
+    normed.clamp_(-tarclip, tarclip)
+  tar_normed[:, -1].zero_()
+  advnorm.normalize(adv, out=adv_normed, update=update)
+  return PpoTargets(adv, tar, tar_normed, adv_normed)
 
 
 def lambda_return(last, term, rew, val, boot, disc, lam):

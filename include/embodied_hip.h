@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports. */
+ * it exports (115 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -39,7 +39,9 @@ extern "C" {
 /* 4 (round 5): + emb_replay_sample_heads, emb_direct_*.  Additions only.        */
 /* 5 (round 6): + emb_comm_exchange_gather, emb_direct_allgather,
  * emb_direct_exchange_gather (additions); emb_configure refuses names that are
- * no knob; a time-out inside emb_direct_* is fatal for the communicator.        */
+ * no knob; a time-out inside emb_direct_* is fatal for the communicator.
+ * Still 5: + emb_normalize, emb_normalize_launches, emb_ppo_targets,
+ * emb_ppo_targets_launches (additions only).                                   */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -532,6 +534,37 @@ int32_t emb_normalize(const emb_normalize_config_t* config, const void* x, int64
 /* Kernel launches emb_normalize has issued in this process, counted where the
  * kernel is launched.                                                         */
 int32_t emb_normalize_launches(int64_t* count);
+
+/* ---- fused PPO targets, float32 on device --------------------------------
+ * The top of ppo_loss (ppo/agent.py:188-210) as ONE kernel launch of one
+ * workgroup, in place of emb_scan_gae, two emb_normalize and the array ops
+ * between them.  Both normalisers must be EMB_NORM_MEANSTD (PPO's own:
+ * ppo/configs.yaml:99-100); their state words are those of emb_normalize.
+ *   agent.py:191-192  (voffset, vscale) = valnorm's stats BEFORE the step,
+ *                     val = pred * vscale + voffset
+ *   agent.py:194-201  GAE over rew, val (B,T) f32 and last, term (B,T) u8 ->
+ *                     adv, tar (B,T-1); live_scale = 1 - 1/hor
+ *   agent.py:203      update != 0: valnorm takes its EMA step from tar (utils.py:44-57)
+ *   agent.py:204-206  tar_normed (B,T) = clip((tar - voffset') / vscale', +-tarclip)
+ *                     with a last column of +0.0; tarclip = 0: no clip
+ *   agent.py:209-210  update != 0: advnorm steps from adv;
+ *                     adv_normed (B,T-1) = (adv - aoffset) / ascale
+ * Words 0-2 of both states are written with update != 0 only, words 3-4
+ * (offset, scale) always.  The batch sums are accumulated in float64, as
+ * emb_normalize's.  Correct at every B >= 1, T >= 2 and alignment; fast while one
+ * workgroup suits B * T (a few thousand values).
+ * EMB_ERR_INVALID before any launch: a NULL config or state, one state given
+ * twice, B < 0, T < 2 with B > 0, B * T > 2^31 - 1, a NULL input or output with
+ * B > 0, an impl other than EMB_NORM_MEANSTD, rate outside [0, 1], tarclip < 0.
+ * B = 0: EMB_OK, nothing is launched.                                           */
+int32_t emb_ppo_targets(const emb_normalize_config_t* valnorm, const emb_normalize_config_t* advnorm,
+                        const void* rew, const void* pred, const void* last, const void* term, int64_t B,
+                        int64_t T, float live_scale, float lam, float tarclip, int32_t update, void* adv,
+                        void* tar, void* tar_normed, void* adv_normed, void* valnorm_state,
+                        void* advnorm_state, void* stream);
+/* Kernel launches emb_ppo_targets has issued in this process, counted where the
+ * kernel is launched.                                                         */
+int32_t emb_ppo_targets_launches(int64_t* count);
 
 /* ----------------------------------------------------------- collectives --
  * The two exchange steps of the sharded path on RCCL directly (xGMI inside one
