@@ -24,7 +24,7 @@ STEPID_BYTES = 20
 U8, I8, I16, I32, I64, F16, BF16, F32, F64, BOOL = range(10)
 LAYOUT_SAME, LAYOUT_CHANNELS_FIRST = 0, 1
 MODES = {'train': 0, 'report': 1, 'eval': 2}
-NORM_MEANSTD, NORM_PERC = 1, 2
+NORM_NONE, NORM_MEANSTD, NORM_PERC = 0, 1, 2
 
 
 class EmbError(RuntimeError):
@@ -199,6 +199,9 @@ SIGNATURES = {
     'emb_normalize_launches': [p],
     'emb_ppo_targets': [p, p, p, p, p, p, i64, i64, f32, f32, f32, i32, p, p, p, p, p, p, p],
     'emb_ppo_targets_launches': [p],
+    'emb_scan_lambda_cont': [p, p, p, i64, i64, f32, f32, p, p],
+    'emb_dreamer_targets': [p, p, p, p, p, p, i64, i64, f32, f32, i32, p, p, p, p, p, p, p, p, p],
+    'emb_dreamer_targets_launches': [p],
     'emb_synth_env_step': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p],
     'emb_synth_env_step_masked': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p, p, i64, i32, p],
     'emb_env_mask_supported': [i64, i32],
@@ -330,6 +333,7 @@ class _FastApi:
       'emb_comm_exchange_gather': 'ints', 'emb_direct_exchange_gather': 'ints',
       'emb_copy_bytes': 'ints', 'emb_mask_actions_notify': 'ints', 'emb_normalize': 'ints',
       'emb_ppo_targets': 'ppo_targets',
+      'emb_scan_lambda_cont': 'scan_cont', 'emb_dreamer_targets': 'dreamer_targets',
   }
 
   def __init__(self, module):

@@ -14,6 +14,8 @@
  *   obs_stack(addr, 11 args)        emb_obs_stack  (two floats at 7, 8)
  *   scan(addr, 10 or 11 args)       emb_scan_gae / emb_scan_lambda (floats at 6, 7)
  *   ppo_targets(addr, 19 args)      emb_ppo_targets (floats at 8, 9, 10)
+ *   scan_cont(addr, 9 args)         emb_scan_lambda_cont (floats at 5, 6)
+ *   dreamer_targets(addr, 20 args)  emb_dreamer_targets (floats at 8, 9)
  *
  * On x86-64 SysV an int32 parameter reads the low half of the 64-bit register
  * or stack slot it is passed in, so integer-class arguments are all passed as
@@ -189,6 +191,57 @@ static PyObject* call_ppo_targets(PyObject* self, PyObject* const* args, Py_ssiz
                         u64, u64, u64))fn)(
       a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], f[0], f[1], f[2], a[12], a[13], a[14], a[15], a[16],
       a[17], a[18], a[19]);
+  Py_END_ALLOW_THREADS
+  return PyLong_FromLong(status);
+}
+
+/* emb_scan_lambda_cont(rew, con, boot, B, T, disc, lam, ret, stream)                9 */
+static PyObject* call_scan_cont(PyObject* self, PyObject* const* args, Py_ssize_t nargs) {
+  if (nargs != 10) {
+    PyErr_SetString(PyExc_TypeError, "fastcall.scan_cont(addr, 9 arguments)");
+    return NULL;
+  }
+  u64 a[10] = {0};
+  float f[2];
+  for (Py_ssize_t i = 0; i < nargs; ++i) {
+    if (i == 6 || i == 7) {
+      if (as_float(args[i], &f[i - 6]) < 0) return NULL;
+    } else if (as_u64(args[i], &a[i]) < 0) {
+      return NULL;
+    }
+  }
+  void* fn = (void*)(uintptr_t)a[0];
+  int32_t status;
+  Py_BEGIN_ALLOW_THREADS
+  status = ((int32_t(*)(u64, u64, u64, u64, u64, float, float, u64, u64))fn)(
+      a[1], a[2], a[3], a[4], a[5], f[0], f[1], a[8], a[9]);
+  Py_END_ALLOW_THREADS
+  return PyLong_FromLong(status);
+}
+
+/* emb_dreamer_targets(retnorm, valnorm, advnorm, rew, con, pred, N, T, disc, lam, update, ret, weight, adv,
+ *                     adv_normed, tar_padded, ret_state, val_state, adv_state, stream)              20 */
+static PyObject* call_dreamer_targets(PyObject* self, PyObject* const* args, Py_ssize_t nargs) {
+  if (nargs != 21) {
+    PyErr_SetString(PyExc_TypeError, "fastcall.dreamer_targets(addr, 20 arguments)");
+    return NULL;
+  }
+  u64 a[21] = {0};
+  float f[2];
+  for (Py_ssize_t i = 0; i < nargs; ++i) {
+    if (i == 9 || i == 10) {
+      if (as_float(args[i], &f[i - 9]) < 0) return NULL;
+    } else if (as_u64(args[i], &a[i]) < 0) {
+      return NULL;
+    }
+  }
+  void* fn = (void*)(uintptr_t)a[0];
+  int32_t status;
+  Py_BEGIN_ALLOW_THREADS
+  status = ((int32_t(*)(u64, u64, u64, u64, u64, u64, u64, u64, float, float, u64, u64, u64, u64, u64, u64, u64,
+                        u64, u64, u64))fn)(
+      a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], f[0], f[1], a[11], a[12], a[13], a[14], a[15], a[16],
+      a[17], a[18], a[19], a[20]);
   Py_END_ALLOW_THREADS
   return PyLong_FromLong(status);
 }
@@ -547,6 +600,10 @@ static PyMethodDef methods[] = {
      "scan(addr, *10 or 11 args) -> status"},
     {"ppo_targets", (PyCFunction)(void (*)(void))call_ppo_targets, METH_FASTCALL,
      "ppo_targets(addr, *19 args) -> status"},
+    {"scan_cont", (PyCFunction)(void (*)(void))call_scan_cont, METH_FASTCALL,
+     "scan_cont(addr, *9 args) -> status"},
+    {"dreamer_targets", (PyCFunction)(void (*)(void))call_dreamer_targets, METH_FASTCALL,
+     "dreamer_targets(addr, *20 args) -> status"},
     {"columns", (PyCFunction)(void (*)(void))call_columns, METH_FASTCALL,
      "columns(steps, plan, out, tensor_type, device) -> None | positions for the slow path"},
     {"stage_plan", (PyCFunction)(void (*)(void))call_stage_plan, METH_FASTCALL,

@@ -152,6 +152,10 @@ hipError_t launch_lambda_return(const uint8_t* last, const uint8_t* term,
                                 const float* rew, const float* boot, int64_t B,
                                 int64_t T, float disc, float lam, float* ret,
                                 hipStream_t stream);
+// The same with last = 0 and term = 1 - con, `con` (B, T) float32 continuation
+// probabilities (dreamerv3/agent.py:401-405).
+hipError_t launch_lambda_return_cont(const float* rew, const float* con, const float* boot, int64_t B,
+                                     int64_t T, float disc, float lam, float* ret, hipStream_t stream);
 
 // One lambda-return problem of emb_scan_lambda_multi (same meaning as the
 // arguments of launch_lambda_return).

@@ -119,6 +119,44 @@ __device__ __forceinline__ void gae_coef4(const float* val, int64_t i, const flo
   }
 }
 
+// The lambda-return's maps with a FLOAT continuation (dreamerv3/agent.py:401-405
+// through :485-489 with last = 0 and term = 1 - con, con the continue head's
+// probability) for `valid` (1..4) consecutive steps of one row whose first step
+// is t0 = i - row start: a step's maps take the NEXT step's reward, continuation
+// and bootstrap value.  The reference's operations in its order: term = 1 - con,
+// live = (1 - term) * disc, cont = lam.  The row's seed is boot[:, -1].  `value`
+// maps every bootstrap value as it is loaded, as gae_coef4's.
+template <typename Value>
+__device__ __forceinline__ void lambda_cont_coef4(const float* rew, const float* con, const float* boot,
+                                                  int64_t i, int valid, float disc, float lam, Value value,
+                                                  float* a, float* bc) {
+  float r[4], c[4], bt[4];
+  if (valid >= 4) {
+    // the usual lane: all three loads issued back to back, one wait
+    const F4 r4 = gload<F4>(rew + i + 1);
+    const F4 c4 = gload<F4>(con + i + 1);
+    const F4 b4 = gload<F4>(boot + i + 1);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      r[k] = r4[k];
+      c[k] = c4[k];
+      bt[k] = b4[k];
+    }
+  } else {
+    load4(rew + i + 1, valid, r);
+    load4(con + i + 1, valid, c);
+    load4(boot + i + 1, valid, bt);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float term = 1.f - c[k];
+    const float live = (1.f - term) * disc;
+    const float cont = lam;
+    a[k] = r[k] + (1.f - cont) * live * value(bt[k]);
+    bc[k] = live * cont;
+  }
+}
+
 // One piece of a row, FOUR steps per lane: lane sl of the segment owns steps
 // t0 .. t0+3 of row b (`valid` of them exist; 0 = a lane right of the row's
 // end or of a row that does not exist), right() is y just right of the piece.

@@ -152,6 +152,38 @@ struct LambdaOp {   // dreamerv3/agent.py:482-490
 };
 static_assert(sizeof(LambdaOp) <= 64, "covered by the kernel-argument preload");
 
+// The lambda-return of imag_loss (dreamerv3/agent.py:401-405 through :482-490):
+// last = 0 and term = 1 - con with `con` the continue head's float probability,
+// which the one-byte flags of LambdaOp cannot carry.
+struct ContLambdaOp {
+  const float* rew; const float* con; const float* boot;
+  float* ret; int32_t T, B; float disc, lam;
+  template <typename F>
+  void unpack(F&& f) const { f(rew, con, boot, ret, T, B, disc, lam); }
+  __host__ __device__ static ContLambdaOp make(const float* rew, const float* con, const float* boot,
+                                               float* ret, int32_t T, int32_t B, float disc, float lam) {
+    return ContLambdaOp{rew, con, boot, ret, T, B, disc, lam};
+  }
+  __device__ float seed(int64_t b) const { return boot[b * T + T - 1]; }
+  __device__ void coef(int64_t b, int64_t t, float& a, float& bc, float& keep) const {
+    const int64_t i = b * T + t;
+    const float term = 1.f - con[i + 1];
+    const float live = (1.f - term) * disc;
+    const float cont = lam;
+    keep = 0.f;
+    a = rew[i + 1] + (1.f - cont) * live * boot[i + 1];
+    bc = live * cont;
+  }
+  __device__ void store(int64_t b, int64_t t, float y, float) const { ret[b * (T - 1) + t] = y; }
+  __device__ void coef4(int64_t b, int t0, int valid, float* a, float* bc, float*) const {
+    lambda_cont_coef4(rew, con, boot, b * T + t0, valid, disc, lam, [](float v) { return v; }, a, bc);
+  }
+  __device__ void store4(int64_t b, int t0, int valid, const float* y, const float*) const {
+    emb::store4(ret + b * (T - 1) + t0, valid, y);
+  }
+};
+static_assert(sizeof(ContLambdaOp) <= 64, "covered by the kernel-argument preload");
+
 // Short rows: a W-lane segment per row, rows longer than W walked right to
 // left with the running value in a register.
 
@@ -373,6 +405,14 @@ hipError_t launch_lambda_return(const uint8_t* last, const uint8_t* term, const 
   if (B > INT32_MAX || T > INT32_MAX) return hipErrorInvalidValue;
   return launch_scan(LambdaOp{last, term, rew, boot, ret, static_cast<int32_t>(T),
                               static_cast<int32_t>(B), disc, lam}, stream);
+}
+
+hipError_t launch_lambda_return_cont(const float* rew, const float* con, const float* boot, int64_t B,
+                                     int64_t T, float disc, float lam, float* ret, hipStream_t stream) {
+  if (B <= 0 || T < 2) return hipSuccess;
+  if (B > INT32_MAX || T > INT32_MAX) return hipErrorInvalidValue;
+  return launch_scan(ContLambdaOp{rew, con, boot, ret, static_cast<int32_t>(T), static_cast<int32_t>(B),
+                                  disc, lam}, stream);
 }
 
 hipError_t launch_lambda_return_multi(int n_problems, const LambdaProblem* problems, hipStream_t stream) {

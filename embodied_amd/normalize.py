@@ -127,7 +127,10 @@ class DeviceNormalize:
   def fused(self, device):
     """(config address, state address) for a launch that runs this normaliser's
     step inside another kernel (`scans.ppo_targets`): the kernel leaves the state
-    words as `emb_normalize` would, (offset, scale) included."""
+    words as `emb_normalize` would, (offset, scale) included.  'none' has
+    neither: (None, None), which such a launch reads as "no normaliser"."""
+    if self.impl == 'none':
+      return None, None
     self._state(device)
     if self._buffer.device != device:
       raise ValueError(f'DeviceNormalize: the statistics are on {self._buffer.device}, the launch on {device}')

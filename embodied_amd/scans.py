@@ -1,7 +1,9 @@
 """Return scans on device (float32): GAE (ppo/agent.py:188-201), lambda-return
-(dreamerv3/agent.py:482-490) and the Director critic target
-(director/agent.py:430-445), each one kernel launch; and the PPO targets
-(ppo/agent.py:188-210: GAE with both return normalisers) as one launch.
+(dreamerv3/agent.py:482-490, over flags and over float continuation
+probabilities) and the Director critic target (director/agent.py:430-445), each
+one kernel launch; the PPO targets (ppo/agent.py:188-210: GAE with both return
+normalisers) and DreamerV3's imagination targets (dreamerv3/agent.py:397-419:
+lambda-return, weight and three return normalisers) as one launch each.
 
 Inputs are torch CUDA tensors; bool flags may be torch.bool or uint8.
 """
@@ -241,7 +243,9 @@ def ppo_targets(rew, pred, last, term, valnorm, advnorm, hor=200, lam=0.8, tarcl
 
 def lambda_return(last, term, rew, val, boot, disc, lam):
   """ret_t = interm_t + live_t*cont_t*ret_{t+1}, seeded with boot[:, -1].
-  All (B,T) -> (B,T-1).  `val` is only shape-checked, as in the reference."""
+  All (B,T) -> (B,T-1).  `val` is only shape-checked, as in the reference.
+  `last` and `term` are flags only (anything not zero is set); float
+  continuation probabilities (imag_loss's term = 1 - con) go to `lambda_return_cont`."""
   dev = _device(rew, boot, last, term)
   rew, boot = _f32(rew, dev), _f32(boot, dev)
   last, term = _flag(last, dev), _flag(term, dev)
@@ -256,6 +260,185 @@ def lambda_return(last, term, rew, val, boot, disc, lam):
       _round32(disc), _round32(lam), ret.data_ptr(),
       _stream(rew))
   return ret
+
+
+def lambda_return_cont(rew, con, boot, disc, lam, out=None):
+  """The lambda-return as imag_loss calls it (dreamerv3/agent.py:401-405): last = 0
+  and term = 1 - con with `con` the continue head's float probability, so
+  live_t = (1 - (1 - con_t)) * disc and cont_t = lam; seeded with boot[:, -1].
+  rew, con, boot (B,T) f32 -> ret (B,T-1).  `out=ret`: write into the caller's
+  contiguous float32 (B,T-1) tensor."""
+  dev = _device(rew, con, boot)
+  rew, con, boot = _f32(rew, dev), _f32(con, dev), _f32(boot, dev)
+  B, T = rew.shape
+  assert con.shape == boot.shape == (B, T)
+  if out is not None:
+    ret = out
+    if not (torch.is_tensor(ret) and ret.__dict__.get('_emb_cont_out') == (B, T, dev)):
+      if (not torch.is_tensor(ret) or ret.dtype != torch.float32 or tuple(ret.shape) != (B, max(T - 1, 0))
+          or ret.device != dev or not ret.is_contiguous()):
+        raise ValueError(f'lambda_return_cont(out=): needs a contiguous float32 {(B, T - 1)} tensor on {dev}')
+      ret._emb_cont_out = (B, T, dev)
+  else:
+    ret = _lib.empty((B, max(T - 1, 0)), torch.float32, dev)
+  if B == 0 or T < 2:
+    return ret                        # nothing to scan: a (B, 0) result
+  fast.emb_scan_lambda_cont(
+      rew.data_ptr(), con.data_ptr(), boot.data_ptr(), B, T, _round32(disc), _round32(lam), ret.data_ptr(),
+      _stream(rew))
+  return ret
+
+
+class DreamerTargets(collections.namedtuple('DreamerTargets', 'ret weight adv adv_normed tar_padded')):
+  """What the top of imag_loss hands on: ret (N,T-1), weight (N,T), adv and
+  adv_normed (N,T-1), the normalised target padded to (N,T)."""
+
+
+# N * (T-1) up to which `dreamer_targets(fused=None)` takes the one-workgroup
+# kernel.  16 384 is structural: the returns' sort keys in one workgroup's LDS
+# (csrc/normalize.h kNormLdsMax).  The kernel beat the composed path at every
+# size of profiles/dreamer_targets_bench.txt up to it, every round of one below
+# every round of the other: 39.9 us against 158.2 at (1024, 16), 43.1 against
+# 164.8 at (1024, 17) = 16 384 returns, 11.4 against 179.1 at (16, 16), 52.6
+# against 7 094 at (16, 1024).  So the constant stays at the limit.
+DREAMER_TARGETS_FUSED_MAX = 16384
+
+
+def dreamer_targets_launches():
+  """Kernel launches `emb_dreamer_targets` has issued in this process."""
+  import ctypes as C
+  count = C.c_int64(0)
+  api.emb_dreamer_targets_launches(C.byref(count))
+  return count.value
+
+
+def _dreamer_targets_path(fused, retnorm, valnorm, advnorm, N, T):
+  """True: the kernel, False: the composed path (`dreamer_targets` says when)."""
+  impls = (retnorm.impl == 'perc' and valnorm.impl in ('meanstd', 'none')
+           and advnorm.impl in ('meanstd', 'none'))
+  size = N * max(T - 1, 0) <= 16384            # one workgroup's LDS, whatever the crossover
+  if fused and not impls:
+    raise ValueError(
+        f"dreamer_targets(fused=True): the kernel runs a 'perc' retnorm with 'meanstd' or 'none' valnorm and "
+        f"advnorm, got '{retnorm.impl}', '{valnorm.impl}' and '{advnorm.impl}' (fused=None or False composes them)")
+  if fused and not size:
+    raise ValueError(
+        f'dreamer_targets(fused=True): {N} x {T - 1} = {N * (T - 1)} returns, the kernel keeps at most 16384 '
+        f'in one workgroup (fused=None or False composes them)')
+  if fused is None:
+    return impls and N * max(T - 1, 0) <= min(DREAMER_TARGETS_FUSED_MAX, 16384)
+  return bool(fused)
+
+
+_DISC = {}
+
+
+def _disc_tensor(disc, dev):
+  """`disc` as a 0-d float32 tensor on `dev`: torch divides by a tensor, but
+  multiplies by the reciprocal of a Python number (one more rounding)."""
+  key = (disc, dev)
+  tensor = _DISC.get(key)
+  if tensor is None:
+    if len(_DISC) > 64:
+      _DISC.clear()
+    tensor = _DISC[key] = torch.tensor(disc, dtype=torch.float32, device=dev)
+  return tensor
+
+
+def _cumprod_rows(x):
+  """cumprod(x, 1) with the products taken left to right, one float32 rounding
+  each -- numpy.cumprod's order, which torch.cumprod's parallel scan does not
+  promise: T-1 dependent column multiplies."""
+  out = torch.empty_like(x)
+  if x.shape[1]:
+    out[:, 0].copy_(x[:, 0])
+  for t in range(1, x.shape[1]):
+    torch.mul(out[:, t - 1], x[:, t], out=out[:, t])
+  return out
+
+
+def dreamer_targets(rew, con, pred, retnorm, valnorm, advnorm, contdisc=True, horizon=333, lam=0.95,
+                    update=True, out=None, fused=None):
+  """The top of imag_loss (dreamerv3/agent.py:397-419): tarval = pred * vscale +
+  voffset with valnorm's statistics before the step, weight = cumprod(disc * con)
+  / disc, the lambda-return with term = 1 - con, `retnorm(ret, update)`,
+  adv = (ret - tarval[:, :-1]) / rscale, `advnorm(adv, update)`, the advantage
+  normalised, `valnorm(ret, update)`, the return normalised and padded with a
+  zero column.  disc = 1 with `contdisc`, else 1 - 1 / horizon.
+  rew, con, pred (N,T) f32 -- `con` the continue head's probability, `pred` the
+  prediction that serves as the target value (`slowvalue.pred()` with slowtar,
+  else `value.pred()`); retnorm, valnorm, advnorm: `DeviceNormalize`
+  -> DreamerTargets(ret (N,T-1), weight (N,T), adv, adv_normed (N,T-1), tar_padded (N,T)).
+
+  Afterwards the three normalisers hold what `retnorm(ret)`, `advnorm(adv)` and
+  `valnorm(ret)` would have left.  Two paths compute it:
+    composed  torch's multiply-add, column multiplies for the weight,
+              `lambda_return_cont`, `retnorm.normalize(ret, sub=tarval[:, :-1])`,
+              `advnorm.normalize`, `valnorm.normalize`, torch's pad: every impl,
+              every size.  The definition.
+    fused     ONE launch of one workgroup (`emb_dreamer_targets`): retnorm 'perc',
+              valnorm and advnorm 'meanstd' or 'none', N * (T-1) <= 16 384.
+  `fused=None` takes the kernel where the impls fit and
+  N * (T-1) <= DREAMER_TARGETS_FUSED_MAX, True / False force a path (True raises
+  where the impls or the size do not fit, and says which).
+  `out=(ret, weight, adv, adv_normed, tar_padded)`: the caller's contiguous
+  float32 tensors; without it one allocation holds all five."""
+  dev = _device(rew, con, pred)
+  rew, con, pred = _f32(rew, dev), _f32(con, dev), _f32(pred, dev)
+  N, T = rew.shape
+  assert con.shape == pred.shape == (N, T)
+  fused = _dreamer_targets_path(fused, retnorm, valnorm, advnorm, N, T)
+  n = max(T - 1, 0)
+  shapes = ((N, n), (N, T), (N, n), (N, n), (N, T))
+  if out is not None:
+    results = tuple(out)
+    if len(results) != 5:
+      raise ValueError('dreamer_targets(out=): needs (ret, weight, adv, adv_normed, tar_padded)')
+    for result, shape in zip(results, shapes):
+      if torch.is_tensor(result) and result.__dict__.get('_emb_dreamer_out') == (shape, dev):
+        continue          # (marked like gae's: an agent hands the same result tensors in again)
+      if (not torch.is_tensor(result) or result.dtype != torch.float32 or tuple(result.shape) != shape
+          or result.device != dev or not result.is_contiguous()):
+        raise ValueError(
+            f'dreamer_targets(out=): needs contiguous float32 tensors of shapes {shapes} on {dev}')
+      result._emb_dreamer_out = (shape, dev)
+  else:
+    # one allocation; every part starts on a 16-byte boundary (the kernel's wide path)
+    sizes = [(rows * cols + 3) // 4 * 4 for rows, cols in shapes]
+    flat = _lib.empty((sum(sizes),), torch.float32, dev)
+    results, start = [], 0
+    for size, (rows, cols) in zip(sizes, shapes):
+      results.append(flat[start:start + rows * cols].view(rows, cols))
+      start += size
+    results = tuple(results)
+  ret, weight, adv, adv_normed, tar_padded = results
+  disc = 1.0 if contdisc else _round32(1 - 1 / horizon)
+  if N == 0 or T < 2:
+    if N and T:           # one column: nothing to scan, the weight is its first factor
+      weight.copy_(con if disc == 1.0 else (con * disc) / _disc_tensor(disc, dev))
+    tar_padded.zero_()
+    return DreamerTargets(ret, weight, adv, adv_normed, tar_padded)
+  if fused:
+    rconfig, rstate = retnorm.fused(dev)
+    vconfig, vstate = valnorm.fused(dev)
+    aconfig, astate = advnorm.fused(dev)
+    fast.emb_dreamer_targets(
+        rconfig, vconfig, aconfig, rew.data_ptr(), con.data_ptr(), pred.data_ptr(), N, T, disc, _round32(lam),
+        int(bool(update)), ret.data_ptr(), weight.data_ptr(), adv.data_ptr(), adv_normed.data_ptr(),
+        tar_padded.data_ptr(), rstate, vstate, astate, _stream(rew))
+    return DreamerTargets(ret, weight, adv, adv_normed, tar_padded)
+  voffset, vscale = valnorm.latest()
+  tarval = pred * vscale + voffset
+  if disc == 1.0:         # (x * 1 and x / 1 are x)
+    weight.copy_(_cumprod_rows(con))
+  else:
+    torch.div(_cumprod_rows(con * disc), _disc_tensor(disc, dev), out=weight)
+  lambda_return_cont(rew, con, tarval, disc, lam, out=ret)
+  retnorm.normalize(ret, sub=tarval[:, :-1].contiguous(), out=adv, update=update)
+  advnorm.normalize(adv, out=adv_normed, update=update)
+  tar_padded[:, :-1].copy_(valnorm.normalize(ret, update=update))
+  tar_padded[:, -1].zero_()
+  return DreamerTargets(ret, weight, adv, adv_normed, tar_padded)
 
 
 _MULTI = {}

@@ -41,7 +41,8 @@ extern "C" {
  * emb_direct_exchange_gather (additions); emb_configure refuses names that are
  * no knob; a time-out inside emb_direct_* is fatal for the communicator.
  * Still 5: + emb_normalize, emb_normalize_launches, emb_ppo_targets,
- * emb_ppo_targets_launches (additions only).                                   */
+ * emb_ppo_targets_launches, emb_scan_lambda_cont, emb_dreamer_targets,
+ * emb_dreamer_targets_launches (additions only).                               */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -473,6 +474,17 @@ int32_t emb_scan_gae_grouped(const void* rew, const void* val, const void* last,
 /* DreamerV3 lambda-return (dreamerv3/agent.py:482-490) -> ret (B,T-1).       */
 int32_t emb_scan_lambda(const void* last, const void* term, const void* rew, const void* boot,
                         int64_t B, int64_t T, float disc, float lam, void* ret, void* stream);
+/* The lambda-return as imag_loss calls it (dreamerv3/agent.py:401-405,482-490):
+ * last = 0 and term = 1 - con, with con (B,T) float32 the continue head's
+ * PROBABILITY (emb_scan_lambda reads one-byte flags: every con < 1 would be
+ * terminal).  Per step, in the reference's operations: term = 1 - con[t+1],
+ * live = (1 - term) * disc, ret[t] = rew[t+1] + (1 - lam) * live * boot[t+1]
+ * + live * lam * ret[t+1], seeded with boot[:, -1].  rew, con, boot (B,T) ->
+ * ret (B,T-1), contiguous float32 on device.
+ * EMB_ERR_INVALID before any launch: a NULL pointer, B < 0, T < 2 with B > 0,
+ * B * T > 2^31 - 1.  B = 0: EMB_OK, nothing is launched.                       */
+int32_t emb_scan_lambda_cont(const void* rew, const void* con, const void* boot, int64_t B, int64_t T,
+                             float disc, float lam, void* ret, void* stream);
 /* Several lambda-return problems of one train step in ONE launch: DreamerV3
  * computes the replay returns (B,T) and the imagined returns (B*K,H+1) in the
  * same step (dreamerv3/agent.py:401-405 imag_loss, :464-466 repl_loss, both
@@ -521,6 +533,7 @@ int32_t emb_abstract_traj(const void* reward, const void* cont, int64_t T, int64
  * EMB_ERR_INVALID before any launch: a NULL config / state (or x with n > 0),
  * n < 0, an unknown impl, rate outside [0, 1], a percentile outside [0, 100],
  * update with n = 0, sub without out.                                          */
+#define EMB_NORM_NONE 0      /* emb_dreamer_targets only: no normaliser, (offset, scale) = (0, 1) */
 #define EMB_NORM_MEANSTD 1
 #define EMB_NORM_PERC 2
 typedef struct emb_normalize_config {
@@ -565,6 +578,45 @@ int32_t emb_ppo_targets(const emb_normalize_config_t* valnorm, const emb_normali
 /* Kernel launches emb_ppo_targets has issued in this process, counted where the
  * kernel is launched.                                                         */
 int32_t emb_ppo_targets_launches(int64_t* count);
+
+/* ---- fused DreamerV3 imagination targets, float32 on device ---------------
+ * imag_loss's targets (dreamerv3/agent.py:397-419) as ONE kernel launch of one
+ * workgroup, in place of emb_scan_lambda_cont, up to three emb_normalize and the
+ * array ops between them.  retnorm must be EMB_NORM_PERC; valnorm and advnorm
+ * are each EMB_NORM_MEANSTD or none (a NULL config or impl EMB_NORM_NONE: its
+ * state is not read, (offset, scale) = (0, 1)); dreamerv3/configs.yaml:111-113
+ * ships perc / none / none.  State words are those of emb_normalize.
+ *   agent.py:397-400  (voffset, vscale) = valnorm's stats BEFORE the step,
+ *                     tarval = pred * vscale + voffset; `pred` (N,T) is the
+ *                     prediction that serves as the target value (the slow
+ *                     critic's with slowtar)
+ *   agent.py:401-402  weight (N,T) = cumprod(disc * con, 1) / disc, the products
+ *                     taken left to right, one rounding each (numpy.cumprod)
+ *   agent.py:403-405  ret (N,T-1) = the lambda-return of emb_scan_lambda_cont
+ *                     over rew, con, boot = tarval
+ *   agent.py:407-408  retnorm(ret, update) -> (roffset, rscale) AFTER the step,
+ *                     adv (N,T-1) = (ret - tarval[:, :-1]) / rscale
+ *   agent.py:409-410  advnorm(adv, update), adv_normed = (adv - aoffset) / ascale
+ *   agent.py:417-419  valnorm(ret, update), tar_padded (N,T) =
+ *                     (ret - voffset') / vscale' with a +0.0 last column
+ * Words 0-2 of every present state are written with update != 0 only, words 3-4
+ * (offset, scale) always.  The percentiles are selected exactly, the batch sums
+ * accumulated in float64, both by the device code of emb_normalize.
+ * One workgroup holds the returns' sort keys: N * (T-1) <= 16 384.
+ * EMB_ERR_INVALID before any launch: a NULL retnorm config or state, retnorm
+ * not EMB_NORM_PERC, valnorm or advnorm EMB_NORM_PERC, a mean-std normaliser
+ * with a NULL state, two states that are read given the same address, N < 0,
+ * T < 2, a NULL input or output with N > 0, N * (T-1) > 16 384 (then:
+ * emb_scan_lambda_cont + emb_normalize), rate outside [0, 1], a percentile
+ * outside [0, 100].  N = 0: EMB_OK, nothing is launched.                        */
+int32_t emb_dreamer_targets(const emb_normalize_config_t* retnorm, const emb_normalize_config_t* valnorm,
+                            const emb_normalize_config_t* advnorm, const void* rew, const void* con,
+                            const void* pred, int64_t N, int64_t T, float disc, float lam, int32_t update,
+                            void* ret, void* weight, void* adv, void* adv_normed, void* tar_padded,
+                            void* ret_state, void* val_state, void* adv_state, void* stream);
+/* Kernel launches emb_dreamer_targets has issued in this process, counted where
+ * the kernel is launched.                                                      */
+int32_t emb_dreamer_targets_launches(int64_t* count);
 
 /* ----------------------------------------------------------- collectives --
  * The two exchange steps of the sharded path on RCCL directly (xGMI inside one
