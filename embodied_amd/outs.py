@@ -1,0 +1,278 @@
+"""Output heads on device: the `symexp_twohot` head of DreamerV3's reward and
+value networks (embodied/jax/heads.py:132-144, embodied/jax/outs.py:273-330).
+
+It sits on both sides of `scans.dreamer_targets`: that function's `pred`
+argument is `value.pred()` / `slowvalue.pred()` and its `tar_padded` result goes
+into `value.loss(...)` (dreamerv3/agent.py:398-399, 420-422, 461-462, 471-473).
+
+Logits are torch CUDA tensors, float32 or bfloat16; the arithmetic is float32.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from ._lib import api
+
+# What the kernels take: a row of at most 1024 bins stays in one wave's
+# registers, indices are 32-bit.  Structural, not a crossover: the fused median
+# is below the composed one at every shape and piece of profiles/twohot_bench.txt
+# -- (16384, 255) f32: pred 16.2 us against 65.8, loss_sum of two targets 27.3
+# against 477.1, backward 44.9 against 95.2; (1008, 255): 15.5 / 52.7, 27.7 /
+# 411.1, 42.0 / 120.8 -- so no size constant sits beside `_path`.  (The backward
+# rows at 16 384 rows have rounds that overlap; the file says how they were timed.)
+TWOHOT_MAX_BINS = 1024
+TWOHOT_MAX_LOGITS = 2 ** 31 - 1
+TWOHOT_MAX_TARGETS = 4
+
+_DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
+
+
+def symexp_twohot_bins(n=255):
+  """The bins of `Head.symexp_twohot` (heads.py:136-143) as a float32 numpy
+  array: symexp of `linspace(-20, 0)` and its mirror image, with one middle bin
+  (exactly 0) for odd `n` and the two middle bins 0.0, -0.0 for even `n`.  Built on the host."""
+  n = int(n)
+  if n < 1:
+    raise ValueError(f'symexp_twohot_bins: n = {n}, needs at least one bin')
+  symexp = lambda x: np.sign(x) * np.expm1(np.abs(x))      # nets.py:63-64
+  if n % 2 == 1:
+    half = symexp(np.linspace(-20, 0, (n - 1) // 2 + 1, dtype=np.float32))
+    bins = np.concatenate([half, -half[:-1][::-1]], 0)
+  else:
+    half = symexp(np.linspace(-20, 0, n // 2, dtype=np.float32))
+    bins = np.concatenate([half, -half[::-1]], 0)
+  assert bins.dtype == np.float32 and bins.shape == (n,)
+  return bins
+
+
+def twohot_launches():
+  """Kernel launches `emb_twohot_stats`, `emb_twohot_loss` and `emb_twohot_grad`
+  have issued in this process."""
+  count = C.c_int64(0)
+  api.emb_twohot_launches(C.byref(count))
+  return count.value
+
+
+def _host_bins(bins, n):
+  """`bins` as a checked float32 numpy array of `n` finite values, none below
+  the one before it.  (Not "strictly increasing": the reference's own bins for an
+  even n hold 0.0 and -0.0 side by side, heads.py:141-143, and its counts
+  `bins <= t`, `bins > t` -- the kernels' too -- are well defined with ties.)"""
+  if torch.is_tensor(bins):
+    bins = bins.detach().cpu().numpy()
+  bins = np.asarray(bins)
+  if bins.dtype != np.float32:
+    raise ValueError(f'TwoHot: bins must be float32 (outs.py:278), got {bins.dtype}')
+  if bins.ndim != 1 or len(bins) != n:
+    raise ValueError(f'TwoHot: {n} logits per row need {n} bins, got shape {bins.shape}')
+  if n < 1 or not np.all(np.isfinite(bins)) or not np.all(bins[1:] >= bins[:-1]):
+    raise ValueError('TwoHot: bins must be finite and increasing (equal neighbours are allowed)')
+  return np.ascontiguousarray(bins)
+
+
+_BINS = {}
+
+
+def _device_bins(host, device):
+  """The bins on `device`: uploaded once per (bins, device)."""
+  key = (host.tobytes(), device)
+  tensor = _BINS.get(key)
+  if tensor is None:
+    if len(_BINS) > 64:
+      _BINS.clear()
+    tensor = _BINS[key] = torch.from_numpy(host.copy()).to(device)
+  return tensor
+
+
+def _path(fused, n, rows):
+  """True: the kernels, False: the composed path (`TwoHot` says when).  The
+  kernels' median was below the composed path's at every shape and piece measured
+  (profiles/twohot_bench.txt), so `fused=None` takes them wherever they fit."""
+  fits = n <= TWOHOT_MAX_BINS and rows * n <= TWOHOT_MAX_LOGITS
+  if fused and n > TWOHOT_MAX_BINS:
+    raise ValueError(
+        f'TwoHot(fused=True): {n} bins, the kernels keep a row of at most {TWOHOT_MAX_BINS} in one wave\'s '
+        'registers (fused=None or False composes it)')
+  if fused and not fits:
+    raise ValueError(
+        f'TwoHot(fused=True): {rows} x {n} logits, the kernels index at most 2^31 - 1 '
+        '(fused=None or False composes it)')
+  if fused is None:
+    return fits
+  return bool(fused)
+
+
+def _check_sum(targets, coefs):
+  """The (targets, coefs) of `loss_sum` as two tuples; refuses what the launch does not take."""
+  targets, coefs = tuple(targets), tuple(float(c) for c in coefs)
+  if len(targets) != len(coefs):
+    raise ValueError(f'TwoHot.loss_sum: {len(targets)} targets and {len(coefs)} coefs')
+  if not 1 <= len(targets) <= TWOHOT_MAX_TARGETS:
+    raise ValueError(
+        f'TwoHot.loss_sum: {len(targets)} targets, one launch takes 1 .. {TWOHOT_MAX_TARGETS} '
+        '(add the results of several calls)')
+  return targets, coefs
+
+
+def _twohot(bins, target):
+  """outs.py:313-327: the two-hot encoding (..., n) of `target` (...)."""
+  n = len(bins)
+  t = target[..., None]
+  below = (bins <= t).to(torch.int32).sum(-1) - 1
+  above = n - (bins > t).to(torch.int32).sum(-1)
+  below = torch.clip(below, 0, n - 1)
+  above = torch.clip(above, 0, n - 1)
+  equal = below == above
+  one = torch.ones((), dtype=torch.float32, device=target.device)
+  dist_to_below = torch.where(equal, one, torch.abs(bins[below] - target))
+  dist_to_above = torch.where(equal, one, torch.abs(bins[above] - target))
+  total = dist_to_below + dist_to_above
+  weight_below = dist_to_above / total
+  weight_above = dist_to_below / total
+  one_hot = torch.nn.functional.one_hot
+  return (one_hot(below, n).to(torch.float32) * weight_below[..., None] +
+          one_hot(above, n).to(torch.float32) * weight_above[..., None])
+
+
+class _FusedLoss(torch.autograd.Function):
+  """`loss_sum` on the kernels: one launch forward, one launch backward."""
+
+  @staticmethod
+  def forward(ctx, logits, head, targets, coefs):
+    lse, _ = head._stats()
+    rows, n = head._x.shape
+    loss = _lib.empty((rows,), torch.float32, logits.device)
+    ctx.head = head
+    ctx.args = ((C.c_void_p * len(targets))(*[t.data_ptr() for t in targets]),
+                (C.c_float * len(coefs))(*coefs), len(targets))
+    ctx.targets = targets                   # keeps the memory behind the addresses
+    api.emb_twohot_loss(
+        head._x.data_ptr(), head._dtype, rows, n, head._bins.data_ptr(), lse.data_ptr(), *ctx.args,
+        loss.data_ptr(), _lib.raw_stream(logits.device))
+    return loss.view(head._lead)
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    head = ctx.head
+    x = head._x
+    rows, n = x.shape
+    gout = gout.to(torch.float32).expand(head._lead).contiguous()
+    grad = torch.empty_like(x)
+    api.emb_twohot_grad(
+        x.data_ptr(), head._dtype, rows, n, head._bins.data_ptr(), head._lse.data_ptr(), *ctx.args,
+        gout.data_ptr(), grad.data_ptr(), _lib.raw_stream(x.device))
+    return grad.view(head._shape), None, None, None
+
+
+class TwoHot:
+  """The reference's `TwoHot` output (outs.py:273-330) over `logits` (..., n), a
+  CUDA tensor of float32 or bfloat16, and `bins`, a float32 numpy array or tensor
+  of n increasing values (`symexp_twohot_bins`; equal neighbours are allowed).  The reference computes
+  in float32 (outs.py:276) and so does this: bfloat16 logits are widened in
+  registers, the gradient comes back in bfloat16.
+
+  `bins` is checked on the host (ValueError) and uploaded once per (bins,
+  device); a device tensor is copied back for that check, so pass the numpy
+  array.  Logits that are not contiguous are made contiguous with one torch op.
+
+  Two paths compute it:
+    composed  torch ops restating the reference line by line: every n.  The
+              definition; about a dozen passes over the logits.
+    fused     `emb_twohot_stats` (one pass: the rows' log-sum-exp and `pred`,
+              kept for the object's life), `emb_twohot_loss` (two logits per row
+              and target) and `emb_twohot_grad` (one read, one write): n <= 1024.
+  `fused=None` takes the kernels where they fit, True / False force a path (True
+  raises where they do not fit, and says why).  No rows: the composed path,
+  nothing is launched."""
+
+  def __init__(self, logits, bins, fused=None):
+    n = logits.shape[-1] if torch.is_tensor(logits) and logits.dim() else np.shape(logits)[-1]
+    host = _host_bins(bins, n)
+    if not (torch.is_tensor(logits) and logits.is_cuda):
+      raise RuntimeError('embodied_amd.outs runs as HIP kernels: pass CUDA tensors (no CPU fallback)')
+    if logits.dtype not in _DTYPES:
+      raise TypeError(f'TwoHot: logits must be float32 or bfloat16, got {logits.dtype}')
+    self.logits = logits
+    self._shape = logits.shape
+    self._lead = logits.shape[:-1]
+    rows = int(np.prod(self._lead, dtype=np.int64))
+    self.fused = _path(fused, n, rows) and rows > 0
+    self._dtype = _DTYPES[logits.dtype]
+    self._bins = _device_bins(host, logits.device)
+    self._x = logits.detach().contiguous().view(rows, n)
+    self._lse = self._pred = None
+
+  def _stats(self):
+    """(lse, pred) of every row: one launch, the first time either is needed."""
+    if self._lse is None:
+      rows, n = self._x.shape
+      lse, pred = _lib.empty((2, rows), torch.float32, self._x.device).unbind(0)
+      api.emb_twohot_stats(
+          self._x.data_ptr(), self._dtype, rows, n, self._bins.data_ptr(), lse.data_ptr(), pred.data_ptr(),
+          _lib.raw_stream(self._x.device))
+      self._lse, self._pred = lse, pred
+    return self._lse, self._pred
+
+  def pred(self):
+    """(...) float32: the symmetric weighted average of outs.py:285-309 -- every
+    mirrored pair p[i] * b[i] + p[n-1-i] * b[n-1-i] is formed before any other
+    addition, so uniform logits over antisymmetric bins give exactly 0.0.
+
+    Carries no gradient: every use of `.pred()` in dreamerv3/agent.py reaches a
+    loss only under `sg` (the lambda-return's bootstrap, the slow regulariser's
+    target, the metrics).  A second call returns the kept result."""
+    if self.fused:
+      return self._stats()[1].view(self._lead)
+    if self._pred is None:
+      with torch.no_grad():
+        bins, n = self._bins, self._x.shape[-1]
+        probs = torch.softmax(self._x.to(torch.float32), -1)
+        if n % 2 == 1:
+          m = (n - 1) // 2
+          p1, p2, p3 = probs[..., :m], probs[..., m: m + 1], probs[..., m + 1:]
+          b1, b2, b3 = bins[:m], bins[m: m + 1], bins[m + 1:]
+          wavg = (p2 * b2).sum(-1) + ((p1 * b1).flip(-1) + (p3 * b3)).sum(-1)
+        else:
+          p1, p2 = probs[..., :n // 2], probs[..., n // 2:]
+          b1, b2 = bins[:n // 2], bins[n // 2:]
+          wavg = ((p1 * b1).flip(-1) + (p2 * b2)).sum(-1)
+        self._pred = wavg
+    return self._pred.view(self._lead)
+
+  def _target(self, target):
+    if not torch.is_tensor(target):
+      target = torch.as_tensor(np.asarray(target, np.float32))
+    target = target.detach().to(device=self.logits.device, dtype=torch.float32)
+    if target.shape != self._lead:
+      raise ValueError(f'TwoHot.loss: target of shape {tuple(target.shape)}, the logits need {tuple(self._lead)}')
+    return target.contiguous()
+
+  def loss(self, target):
+    """(...) float32: outs.py:311-330, the cross entropy against the two-hot
+    encoding of `target` (...) float32.  Differentiable with respect to the
+    logits (once); the target is a constant, as under the reference's `sg`.
+    A NaN target gives a NaN loss; a target beyond an outer bin lands on it."""
+    return self.loss_sum((target,), (1.0,))
+
+  def loss_sum(self, targets, coefs):
+    """sum_k coefs[k] * loss(targets[k]) for 1 .. 4 targets, the terms added in
+    the order given -- `value.loss(tar_padded) + slowreg * value.loss(slowvalue.pred())`
+    (agent.py:420-422) is `loss_sum((tar_padded, slow), (1.0, slowreg))`.  On the
+    kernels that is ONE launch forward and ONE backward whatever the count."""
+    targets, coefs = _check_sum(targets, coefs)
+    targets = tuple(self._target(t) for t in targets)
+    if self.fused:
+      return _FusedLoss.apply(self.logits, self, targets, coefs)
+    logits = self.logits.to(torch.float32)
+    log_pred = logits - torch.logsumexp(logits, -1, keepdim=True)
+    total = None
+    for target, coef in zip(targets, coefs):
+      with torch.no_grad():
+        twohot = _twohot(self._bins, target)
+      term = coef * -(twohot * log_pred).sum(-1)
+      total = term if total is None else total + term
+    return total

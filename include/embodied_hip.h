@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports (115 functions). */
+ * it exports (122 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -42,7 +42,8 @@ extern "C" {
  * no knob; a time-out inside emb_direct_* is fatal for the communicator.
  * Still 5: + emb_normalize, emb_normalize_launches, emb_ppo_targets,
  * emb_ppo_targets_launches, emb_scan_lambda_cont, emb_dreamer_targets,
- * emb_dreamer_targets_launches (additions only).                               */
+ * emb_dreamer_targets_launches, emb_twohot_stats, emb_twohot_loss,
+ * emb_twohot_grad, emb_twohot_launches (additions only).                       */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -617,6 +618,56 @@ int32_t emb_dreamer_targets(const emb_normalize_config_t* retnorm, const emb_nor
 /* Kernel launches emb_dreamer_targets has issued in this process, counted where
  * the kernel is launched.                                                      */
 int32_t emb_dreamer_targets_launches(int64_t* count);
+
+/* ---- the symexp_twohot head, float32 arithmetic on device -----------------
+ * DreamerV3's reward and value heads (embodied/jax/heads.py:132-144 builds the
+ * bins, embodied/jax/outs.py:273-330 is the distribution): what sits on both
+ * sides of emb_dreamer_targets -- its `pred` argument is value.pred(), its
+ * tar_padded goes into value.loss (dreamerv3/agent.py:398-399,420-422).
+ * `logits` is (rows, n) contiguous on device, dtype EMB_F32 or EMB_BF16 (bfloat16
+ * is widened in registers; the reference computes in float32, outs.py:276);
+ * `bins` n float32 on device, non-decreasing (the caller's promise: the library
+ * counts, it does not sort; heads.py:141-143 gives an even n the neighbours
+ * 0.0, -0.0); lse, pred, loss, gout, every target: `rows` float32 on device.
+ * One kernel launch each:
+ *   emb_twohot_stats  outs.py:280,285-309,328-329: lse = max + log(sum(exp(x - max)))
+ *                     and pred = sum over the mirrored pairs
+ *                     p[i] * b[i] + p[n-1-i] * b[n-1-i], each pair formed before
+ *                     any other addition, plus the middle bin for odd n, with
+ *                     p = exp(x - max) / sum: uniform logits over antisymmetric
+ *                     bins give exactly 0.0.  One pass over the logits.
+ *   emb_twohot_loss   outs.py:311-330 for k targets (host array of k device
+ *                     pointers) with k host coefficients:
+ *                       below = #(bins <= t) - 1, above = n - #(bins > t), both
+ *                       clipped to [0, n-1]; equal indices: weights 0.5 / 0.5 on
+ *                       the one bin, else w_below = |b[above] - t| / total,
+ *                       w_above = |b[below] - t| / total
+ *                       loss[r] = sum_k coefs[k] * -(w_below * (x[below] - lse)
+ *                                                   + w_above * (x[above] - lse))
+ *                     Two logits per row and target are read, not the row.  A NaN
+ *                     target gives NaN (n > 1), one beyond an outer bin that bin
+ *                     with weight 1.
+ *   emb_twohot_grad   the gradient of that sum with respect to the logits,
+ *                       grad[r, i] = gout[r] * (sum(coefs) * exp(x[r, i] - lse[r])
+ *                                               - sum_k coefs[k] * twohot_k[r, i])
+ *                     written in the logits' dtype: one read of the logits, one
+ *                     write of the gradient.
+ * No atomics: the same bits run to run.
+ * EMB_ERR_INVALID before any launch: an unknown dtype, rows < 0, n outside
+ * 1 .. 1024, rows * n > 2^31 - 1, k outside 1 .. 4, a NULL targets or coefs
+ * array, and with rows > 0 any NULL pointer.  rows = 0: EMB_OK, nothing is
+ * launched.                                                                    */
+int32_t emb_twohot_stats(const void* logits, int32_t dtype, int64_t rows, int64_t n, const void* bins, void* lse,
+                         void* pred, void* stream);
+int32_t emb_twohot_loss(const void* logits, int32_t dtype, int64_t rows, int64_t n, const void* bins,
+                        const void* lse, const void* const* targets, const float* coefs, int32_t k, void* loss,
+                        void* stream);
+int32_t emb_twohot_grad(const void* logits, int32_t dtype, int64_t rows, int64_t n, const void* bins,
+                        const void* lse, const void* const* targets, const float* coefs, int32_t k, const void* gout,
+                        void* grad, void* stream);
+/* Kernel launches the three entry points above have issued in this process,
+ * counted where the kernels are launched.                                      */
+int32_t emb_twohot_launches(int64_t* count);
 
 /* ----------------------------------------------------------- collectives --
  * The two exchange steps of the sharded path on RCCL directly (xGMI inside one
