@@ -187,7 +187,16 @@ class TwoHot:
               and target) and `emb_twohot_grad` (one read, one write): n <= 1024.
   `fused=None` takes the kernels where they fit, True / False force a path (True
   raises where they do not fit, and says why).  No rows: the composed path,
-  nothing is launched."""
+  nothing is launched.
+
+  Non-finite logits: a NaN or +inf logit, or a row of -inf, makes that row's
+  `pred`, loss and gradient NaN on both paths, and no other row's.  One -inf
+  logit is a bin of probability 0; `pred` and the gradient stay finite.  Its
+  LOSS differs between the paths: composed is the definition, the product with
+  the two-hot target over the whole row, NaN (0 * -inf) unless the -inf bin
+  carries weight (then +inf); fused reads the two logits at `below` and `above`
+  alone, so a -inf logit in any other bin is not seen and the loss is finite.
+  DESIGN.md says why that stands."""
 
   def __init__(self, logits, bins, fused=None):
     n = logits.shape[-1] if torch.is_tensor(logits) and logits.dim() else np.shape(logits)[-1]
@@ -268,7 +277,10 @@ class TwoHot:
     if self.fused:
       return _FusedLoss.apply(self.logits, self, targets, coefs)
     logits = self.logits.to(torch.float32)
-    log_pred = logits - torch.logsumexp(logits, -1, keepdim=True)
+    # logits - logsumexp(logits) as one op, whose backward makes a row with a
+    # +inf logit NaN throughout, as the closed form and the kernel do (the
+    # subtraction's backward leaves a single NaN in it)
+    log_pred = torch.log_softmax(logits, -1)
     total = None
     for target, coef in zip(targets, coefs):
       with torch.no_grad():

@@ -13,6 +13,7 @@ from tests import twohot_cases as cases
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 GOLDEN = ROOT / 'tests' / 'golden' / 'twohot.npz'
+EDGES = ROOT / 'tests' / 'golden' / 'twohot_edges.npz'
 NAMES = ('emb_twohot_stats', 'emb_twohot_loss', 'emb_twohot_grad', 'emb_twohot_launches')
 
 
@@ -74,11 +75,83 @@ def test_fixture_is_current():
   spec = importlib.util.spec_from_file_location('_gen_twohot', ROOT / 'tools' / 'gen_twohot_golden.py')
   tool = importlib.util.module_from_spec(spec)
   spec.loader.exec_module(tool)
-  fresh = tool.generate()
-  with np.load(GOLDEN) as f:
-    assert sorted(f.files) == sorted(fresh)
-    for key in f.files:
-      assert np.array_equal(f[key], fresh[key], equal_nan=f[key].dtype.kind == 'f'), key
+  for path, fresh in ((GOLDEN, tool.generate()), (EDGES, tool.generate_edges())):
+    with np.load(path) as f:
+      assert sorted(f.files) == sorted(fresh)
+      for key in f.files:
+        assert np.array_equal(f[key], fresh[key], equal_nan=f[key].dtype.kind == 'f'), (path.name, key)
+
+
+def test_edges_fixture_matches_its_digests_and_the_restatement():
+  """`cases.reference64` against the reference's own float64 run where the first
+  fixture does not reach: bins that are not the symexp set (asymmetric, runs of
+  equal neighbours, equal outer bins), the zeros / denormals / outer bins of the
+  even symexp set as targets, and logits with -inf, +inf, NaN and |x| up to 1e4.
+  The bars of the test above; NaN and +-inf where and only where the class has them."""
+  from embodied_amd import outs
+  with np.load(EDGES) as f:
+    assert tuple(f['twohot_lines']) == (273, 330)
+    assert f['bins_symexp64'].tobytes() == outs.symexp_twohot_bins(64).tobytes()
+    seen = set()
+    for case, c in enumerate(cases.EDGE_CASES):
+      name = cases.edge_tag(case)
+      bins = cases.edge_bins(c.bins, c.n, outs.symexp_twohot_bins)
+      assert bins.tobytes() == f[f'bins_{c.bins}{c.n}'].tobytes(), name
+      assert np.array_equal(outs._host_bins(bins, c.n), bins)             # what the facade takes
+      inp = cases.edge_inputs(case, bins)
+      assert np.array_equal(f[f'in_{name}'], cases.digest(inp)), name
+      targets = [inp[f'target{k}'] for k in range(cases.EDGE_TARGETS)]
+      pred64, loss64 = f[f'pred64_{name}'], f[f'loss64_{name}']
+      assert pred64.shape == (cases.EDGE_ROWS,) and loss64.shape == (cases.EDGE_TARGETS, cases.EDGE_ROWS)
+      assert pred64.dtype == loss64.dtype == np.float64
+      ref = cases.reference64(inp['logits'], bins, targets)
+      loss = np.stack(ref['loss'])
+      assert np.array_equal(np.isnan(ref['pred']), np.isnan(pred64)), name
+      assert np.array_equal(np.isnan(loss), np.isnan(loss64)), name
+      assert np.array_equal(np.isposinf(loss), np.isposinf(loss64)) and not np.isneginf(loss64).any(), name
+      ok = ~np.isnan(pred64)
+      assert np.all(np.abs(ref['pred'] - pred64)[ok] <= 1e-12 * (1 + ref['scale'][ok])), name
+      assert np.allclose(loss, loss64, rtol=1e-12, atol=1e-12, equal_nan=True), name
+      # the two-bin sum is the definition wherever the row's logits are finite
+      finite = np.isfinite(inp['logits']).all(-1)
+      assert np.allclose(np.stack(ref['loss2'])[:, finite], loss64[:, finite], rtol=1e-12, atol=1e-12), name
+      if c.logits == 'normal':
+        assert np.isfinite(pred64).all() and np.isfinite(loss64).all(), name
+      else:
+        kinds = np.array(cases.EDGE_KINDS)[np.arange(cases.EDGE_ROWS) % len(cases.EDGE_KINDS)]
+        assert np.isnan(pred64[np.isin(kinds, ('all_ninf', 'pinf', 'nan'))]).all(), name
+        assert np.isfinite(pred64[~np.isin(kinds, ('all_ninf', 'pinf', 'nan'))]).all(), name
+        assert np.isfinite(loss64[:, np.isin(kinds, ('finite', 'big'))]).all(), name
+        # a -inf logit: +inf under a weight, NaN (0 * -inf) under none -- never finite for n > 2
+        assert not np.isfinite(loss64[:, np.isin(kinds, ('ninf_below', 'ninf_above', 'ninf_else'))]).any(), name
+        assert np.isposinf(loss64[0, kinds == 'ninf_below']).all() and np.isnan(loss64[0, kinds == 'ninf_else']).all(), name
+        seen |= {(k, 'inf' if np.isposinf(v) else 'nan') for k, v in zip(kinds, loss64[0]) if k == 'ninf_above'}
+      if c.bins == 'ties':
+        assert (np.diff(bins) == 0).sum() >= 4 and bins[0] == bins[1] and bins[-1] == bins[-2], name
+        assert any(np.isin(t, bins[np.r_[np.diff(bins) == 0, False]]).any() for t in targets), name
+      if c.bins == 'symexp':
+        assert np.array_equal(targets[0][:6].view(np.uint32),
+                              np.array([0.0, -0.0, cases.DENORMAL, -cases.DENORMAL, bins[-1], bins[0]], np.float32).view(np.uint32))
+    assert ('ninf_above', 'inf') in seen
+  assert EDGES.stat().st_size < 100_000
+
+
+def test_float32_restatement_sits_inside_the_bars_of_three_and_four_targets():
+  """The bars of `test_three_and_four_targets` come from the sums' condition
+  scales, not from the kernels: float32 numpy over the same seeds must fit."""
+  from tests import test_gpu_twohot as device
+  worst = [0.0, 0.0]
+  for k in (3, 4):
+    for rows, n in ((5, 63), (67, 255), (1025, 2)):
+      for kind in ('f32', 'bf16'):
+        d = device._multi(n, rows, kind)
+        coefs = device.COEFS4[:k]
+        loss, grad = cases.composed32(d['logits'], d['bins'], d['targets'][:k], coefs, d['gout'])
+        want_loss, loss_bar, want_grad, grad_bar = device._sum_bars(d['ref'], coefs, d['gout'])
+        worst[0] = max(worst[0], device._match(loss, want_loss, loss_bar))
+        worst[1] = max(worst[1], device._match(grad, want_grad, grad_bar))
+  print(f'float32 numpy, three and four targets: loss {worst[0]:.3g}, grad {worst[1]:.3g} of their bars')
+  assert max(worst) <= 1.0, worst
 
 
 def test_header_declares_and_binding_covers_the_new_symbols():

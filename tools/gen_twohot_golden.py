@@ -1,4 +1,4 @@
-"""Generate tests/golden/twohot.npz by EXECUTING the reference's own `TwoHot`
+"""Generate tests/golden/twohot.npz and tests/golden/twohot_edges.npz by EXECUTING the reference's own `TwoHot`
 class with the `Output` class it inherits from (embodied/jax/outs.py),
 `nets.symexp` (embodied/jax/nets.py) and the bin construction of
 `Head.symexp_twohot` (embodied/jax/heads.py) under numpy stand-ins.
@@ -30,6 +30,13 @@ a bin, and numpy sums pairwise where XLA reduces in its own order.
 
 Only data is written: the bins per n, per case the inputs' digest, `pred` and
 the loss per target in both precisions, and the reference's line numbers.
+
+twohot_edges.npz (`generate_edges`) is the float64 run of the same class over
+`tests.twohot_cases.EDGE_CASES`: bins that are not the symexp set (asymmetric,
+with runs of equal neighbours), logits with -inf, +inf, NaN and magnitudes up
+to 1e4, four target sets per case at every edge of the two counts.  It is what
+`tests.twohot_cases.reference64` is held against before the GPU tests use it
+there.
 """
 import ast
 import pathlib
@@ -126,6 +133,27 @@ def generate():
   return out
 
 
+def generate_edges():
+  TwoHot64, class_lines = reference_classes(np.float64)
+  build, _, _ = head_of(reference_classes(np.float32)[0])
+  symexp_bins = lambda n: np.asarray(build(np.zeros((1, n), np.float32), n).bins)
+  out = {'twohot_lines': np.array(class_lines)}
+  for kind, n in cases.EDGE_SETS:
+    out[f'bins_{kind}{n}'] = cases.edge_bins(kind, n, symexp_bins)
+  for case, c in enumerate(cases.EDGE_CASES):
+    bins = out[f'bins_{c.bins}{c.n}']
+    inp = cases.edge_inputs(case, bins)
+    name = cases.edge_tag(case)
+    out[f'in_{name}'] = cases.digest(inp)
+    with np.errstate(all='ignore'):
+      head64 = TwoHot64(inp['logits'].astype(np.float64), bins.astype(np.float64))
+      pred64 = head64.pred()
+      loss64 = np.stack([head64.loss(inp[f'target{k}'].astype(np.float64)) for k in range(cases.EDGE_TARGETS)])
+    assert pred64.dtype == loss64.dtype == np.float64
+    out[f'pred64_{name}'], out[f'loss64_{name}'] = pred64, loss64
+  return out
+
+
 def main():
   out = generate()
   path = ROOT / 'tests' / 'golden' / 'twohot.npz'
@@ -133,6 +161,12 @@ def main():
   size = path.stat().st_size
   assert size < 900_000, size
   print(f'twohot: {len(cases.CASES)} cases, {len(out)} arrays, {size} bytes')
+  out = generate_edges()
+  path = ROOT / 'tests' / 'golden' / 'twohot_edges.npz'
+  np.savez_compressed(path, **out)
+  size = path.stat().st_size
+  assert size < 100_000, size
+  print(f'twohot_edges: {len(cases.EDGE_CASES)} cases, {len(out)} arrays, {size} bytes')
 
 
 if __name__ == '__main__':
