@@ -1,5 +1,7 @@
 """Output heads on device: the `symexp_twohot` head of DreamerV3's reward and
-value networks (embodied/jax/heads.py:132-144, embodied/jax/outs.py:273-330).
+value networks (embodied/jax/heads.py:132-144, embodied/jax/outs.py:273-330),
+and the one-hot latents' KL pair of its world model (`OneHot`, `rssm_kl`:
+dreamerv3/rssm.py:123-132, embodied/jax/outs.py:40-76, 208-263).
 
 It sits on both sides of `scans.dreamer_targets`: that function's `pred`
 argument is `value.pred()` / `slowvalue.pred()` and its `tar_padded` result goes
@@ -288,3 +290,277 @@ class TwoHot:
       term = coef * -(twohot * log_pred).sum(-1)
       total = term if total is None else total + term
     return total
+
+
+# ---- OneHot: the RSSM's latent distribution, its KL pair and entropies ------
+
+# What the kernels take: a group of at most 256 classes stays in one wave's
+# registers, indices are 32-bit.  Structural, not a crossover: the fused median
+# is below the composed one at all 24 rows of profiles/rssm_kl_bench.txt (rows
+# 1024 and 16 384, (32, 32), (32, 64), (32, 96), float32 and bfloat16, forward and
+# forward + backward) -- (16384, 32, 64) bf16: forward 261.1 us against 3926.7,
+# forward + backward 518.5 against 5085.3; (1024, 32, 32) f32: 24.2 / 292.9 and
+# 122.8 / 693.6 -- so no size constant sits beside `_kl_path`.
+ONEHOT_MAX_CLASSES = 256
+ONEHOT_MAX_LOGITS = 2 ** 31 - 1
+
+
+def onehot_kl_launches():
+  """Kernel launches `emb_onehot_kl` and `emb_onehot_kl_grad` have issued in
+  this process."""
+  count = C.c_int64(0)
+  api.emb_onehot_kl_launches(C.byref(count))
+  return count.value
+
+
+def _kl_path(fused, rows, stoch, classes):
+  """True: the kernels, False: the composed path (`rssm_kl` says when).
+  The kernels' median was below the composed path's at every shape, dtype and
+  piece measured (profiles/rssm_kl_bench.txt), so `fused=None` takes them
+  wherever they fit."""
+  fits = 1 <= classes <= ONEHOT_MAX_CLASSES and stoch >= 1 and rows * stoch * classes <= ONEHOT_MAX_LOGITS
+  if fused and not 1 <= classes <= ONEHOT_MAX_CLASSES:
+    raise ValueError(
+        f'OneHot(fused=True): {classes} classes, the kernels keep a group of at most {ONEHOT_MAX_CLASSES} in one '
+        'wave\'s registers (fused=None or False composes it)')
+  if fused and not fits:
+    raise ValueError(
+        f'OneHot(fused=True): {rows} x {stoch} x {classes} logits, the kernels index 1 .. 2^31 - 1 '
+        '(fused=None or False composes it)')
+  if fused is None:
+    return fits
+  return bool(fused)
+
+
+def _onehot_logits(logits, unimix):
+  """outs.py:210-217, `Categorical.__init__`."""
+  logits = logits.to(torch.float32)
+  if unimix:
+    probs = torch.softmax(logits, -1)
+    uniform = torch.ones_like(probs) / probs.shape[-1]
+    probs = (1 - unimix) * probs + unimix * uniform
+    logits = torch.log(probs)
+  return logits
+
+
+def _composed_kl(logits, other):
+  """outs.py:236-240 under `Agg(..., 1, sum)` (outs.py:73-76)."""
+  logprob = torch.log_softmax(logits, -1)
+  logother = torch.log_softmax(other, -1)
+  prob = torch.softmax(logits, -1)
+  return (prob * (logprob - logother)).sum(-1).sum(-1)
+
+
+def _composed_entropy(logits):
+  """outs.py:230-234 under `Agg(..., 1, sum)` (outs.py:69-71)."""
+  logprob = torch.log_softmax(logits, -1)
+  prob = torch.softmax(logits, -1)
+  return (-(prob * logprob).sum(-1)).sum(-1)
+
+
+def _kl_forward(x, y, dtype, unimix, free_nats):
+  """One launch: (kl, ent_post, ent_prior, dyn, rep), each (rows,) float32."""
+  rows, stoch, classes = x.shape
+  out = _lib.empty((5, rows), torch.float32, x.device)
+  kl, ent_post, ent_prior, dyn, rep = out.unbind(0)
+  api.emb_onehot_kl(
+      x.data_ptr(), y.data_ptr(), dtype, rows, stoch, classes, unimix, free_nats, kl.data_ptr(),
+      ent_post.data_ptr(), ent_prior.data_ptr(), dyn.data_ptr(), rep.data_ptr(), _lib.raw_stream(x.device))
+  return kl, ent_post, ent_prior, dyn, rep
+
+
+def _kl_backward(x, y, dtype, unimix, free_nats, kl, g_rep, g_dyn, lead):
+  """One launch: (grad_post, grad_prior); a side whose upstream gradient is None
+  is not written and comes back None."""
+  rows, stoch, classes = x.shape
+  row_grad = lambda g: None if g is None else g.to(torch.float32).expand(lead).contiguous()
+  g_rep, g_dyn = row_grad(g_rep), row_grad(g_dyn)
+  if g_rep is None and g_dyn is None:
+    return None, None
+  grad_post = None if g_rep is None else torch.empty_like(x)
+  grad_prior = None if g_dyn is None else torch.empty_like(y)
+  address = lambda t: None if t is None else t.data_ptr()
+  api.emb_onehot_kl_grad(
+      x.data_ptr(), y.data_ptr(), dtype, rows, stoch, classes, unimix, free_nats, kl.data_ptr(), address(g_rep),
+      address(g_dyn), address(grad_post), address(grad_prior), _lib.raw_stream(x.device))
+  return grad_post, grad_prior
+
+
+class _FusedRssmKL(torch.autograd.Function):
+  """(dyn, rep, dyn_ent, rep_ent) on the kernels: one launch forward, one
+  backward.  dyn's gradient goes to prior, rep's to post."""
+
+  @staticmethod
+  def forward(ctx, post, prior, unimix, free_nats):
+    x, y = (t.detach().contiguous().view(-1, *t.shape[-2:]) for t in (post, prior))
+    lead = post.shape[:-2]
+    kl, ent_post, ent_prior, dyn, rep = _kl_forward(x, y, _DTYPES[post.dtype], unimix, free_nats)
+    ctx.saved = (x, y, kl, _DTYPES[post.dtype], unimix, free_nats, lead, post.shape)
+    ctx.set_materialize_grads(False)
+    dyn, rep, dyn_ent, rep_ent = (t.view(lead) for t in (dyn, rep, ent_prior, ent_post))
+    ctx.mark_non_differentiable(dyn_ent, rep_ent)
+    return dyn, rep, dyn_ent, rep_ent
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, g_dyn, g_rep, _dyn_ent, _rep_ent):
+    x, y, kl, dtype, unimix, free_nats, lead, shape = ctx.saved
+    needs = ctx.needs_input_grad
+    grad_post, grad_prior = _kl_backward(
+        x, y, dtype, unimix, free_nats, kl, g_rep if needs[0] else None, g_dyn if needs[1] else None, lead)
+    view = lambda g: None if g is None else g.view(shape)
+    return view(grad_post), view(grad_prior), None, None
+
+
+class _FusedKL(torch.autograd.Function):
+  """`OneHot.kl(other)` on the kernels: the raw kl, its gradient to both operands."""
+
+  @staticmethod
+  def forward(ctx, logits, other, unimix):
+    x, y = (t.detach().contiguous().view(-1, *t.shape[-2:]) for t in (logits, other))
+    lead = logits.shape[:-2]
+    kl = _kl_forward(x, y, _DTYPES[logits.dtype], unimix, 0.0)[0]
+    ctx.saved = (x, y, kl, _DTYPES[logits.dtype], unimix, lead, logits.shape)
+    ctx.set_materialize_grads(False)
+    return kl.view(lead)
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    x, y, kl, dtype, unimix, lead, shape = ctx.saved
+    needs = ctx.needs_input_grad
+    grad_self, grad_other = _kl_backward(
+        x, y, dtype, unimix, 0.0, kl, gout if needs[0] else None, gout if needs[1] else None, lead)
+    view = lambda g: None if g is None else g.view(shape)
+    return view(grad_self), view(grad_other), None
+
+
+def _check_onehot(who, logits):
+  if not (torch.is_tensor(logits) and logits.is_cuda):
+    raise RuntimeError('embodied_amd.outs runs as HIP kernels: pass CUDA tensors (no CPU fallback)')
+  if logits.dtype not in _DTYPES:
+    raise TypeError(f'{who}: logits must be float32 or bfloat16, got {logits.dtype}')
+  if logits.dim() < 2:
+    raise ValueError(f'{who}: logits of shape {tuple(logits.shape)}, needs (..., stoch, classes)')
+
+
+def _check_pair(who, post, prior):
+  _check_onehot(who, post)
+  _check_onehot(who, prior)
+  if post.shape != prior.shape:
+    raise ValueError(f'{who}: logits of shapes {tuple(post.shape)} and {tuple(prior.shape)}')
+  if post.dtype != prior.dtype or post.device != prior.device:
+    raise TypeError(f'{who}: logits of {post.dtype} on {post.device} and {prior.dtype} on {prior.device}')
+
+
+def _check_unimix(who, unimix):
+  unimix = float(unimix)
+  if not 0.0 <= unimix < 1.0:
+    raise ValueError(f'{who}: unimix = {unimix}, needs 0 <= unimix < 1')
+  return unimix
+
+
+def _rows_of(logits):
+  return int(np.prod(logits.shape[:-2], dtype=np.int64))
+
+
+class OneHot:
+  """The reference's `Agg(OneHot(logits, unimix), 1, sum)` (rssm.py:173-176,
+  outs.py:40-76, 208-263) over `logits` (..., stoch, classes), a CUDA tensor of
+  float32 or bfloat16: `.entropy()` and `.kl(other)`, each (...) float32.  The
+  reference computes in float32 (outs.py:211) and so does this; bfloat16 logits
+  are widened in registers and the gradients come back in bfloat16.
+
+  Two paths, as `TwoHot`: composed restates the reference line by line in torch
+  (the definition, every size); fused is `emb_onehot_kl` / `emb_onehot_kl_grad`,
+  classes <= 256.  `fused=None` takes the kernels where they fit, True / False
+  force a path (True raises where they do not fit, and says why).  No rows: the
+  composed path, nothing is launched.  `rssm_kl` documents the arithmetic and
+  the non-finite logits."""
+
+  def __init__(self, logits, unimix=0.0, fused=None):
+    _check_onehot('OneHot', logits)
+    self.logits = logits
+    self.unimix = _check_unimix('OneHot', unimix)
+    self._lead = logits.shape[:-2]
+    rows = _rows_of(logits)
+    self._fused_arg = fused
+    self.fused = _kl_path(fused, rows, *logits.shape[-2:]) and rows > 0
+
+  def entropy(self):
+    """(...) float32, no gradient: the reference uses it for metrics only
+    (rssm.py:131-132).  On the kernels: the forward launch with these logits on
+    both sides."""
+    with torch.no_grad():
+      if self.fused:
+        x = self.logits.detach().contiguous().view(-1, *self.logits.shape[-2:])
+        return _kl_forward(x, x, _DTYPES[x.dtype], self.unimix, 0.0)[1].view(self._lead)
+      return _composed_entropy(_onehot_logits(self.logits, self.unimix))
+
+  def kl(self, other):
+    """(...) float32: kl(self || other), differentiable once with respect to
+    both operands.  `other` is a `OneHot` of the same shape, dtype and unimix."""
+    if not isinstance(other, OneHot):
+      raise TypeError(f'OneHot.kl: other must be a OneHot, got {type(other).__name__}')
+    _check_pair('OneHot.kl', self.logits, other.logits)
+    if other.unimix != self.unimix:
+      raise ValueError(f'OneHot.kl: unimix {self.unimix} against {other.unimix}')
+    if self.fused:
+      return _FusedKL.apply(self.logits, other.logits, self.unimix)
+    return _composed_kl(_onehot_logits(self.logits, self.unimix), _onehot_logits(other.logits, self.unimix))
+
+
+def rssm_kl(post, prior, unimix=0.01, free_nats=1.0, fused=None):
+  """The KL pair of `RSSM.loss` (rssm.py:123-132) over `post` and `prior`
+  (..., stoch, classes), CUDA tensors of float32 or bfloat16:
+
+      dyn = max(kl(sg(post) || prior), free_nats)      gradient to prior only
+      rep = max(kl(post || sg(prior)), free_nats)      gradient to post only
+      dyn_ent = entropy(prior), rep_ent = entropy(post)      no gradient
+
+  as a dict of four (...) float32 tensors (the metrics' `.mean()` is the
+  caller's).  `free_nats == 0` takes no maximum (rssm.py:127).  On the kernels
+  that is ONE launch forward and ONE backward: dyn and rep have the same value,
+  and both gradients have a closed form.  The maximum's gradient is 1 above
+  free_nats, 0 below and 1/2 at equality, as `jnp.maximum`'s.  An output that
+  takes no part in the loss costs nothing: its side is not written.
+
+  Per group the reference mixes, takes the log, and then runs softmax and
+  log_softmax over that log again (outs.py:212-216, 231-232, 237-239).  The
+  composed path repeats that; the kernels do not: after the mix the
+  probabilities sum to 1 up to rounding, so the second pass is the identity.
+  With `unimix == 0` both work in the log domain (`log_softmax`), finite for a
+  class whose probability underflows.
+
+  Non-finite logits.  A NaN or +inf logit, or a group of -inf, makes that row's
+  dyn and rep and the entropy of the side it is in NaN on both paths and touches
+  no other row (the other side's entropy is what it was).  Its gradients: on the
+  kernels the whole row's, on both sides, are NaN (a NaN kl is on neither side
+  of free_nats); composed is the definition, NaN in the poisoned group on both
+  sides and whatever autograd leaves in the row's other groups.  With
+  `unimix > 0` a -inf logit is a class of probability unimix / classes and
+  everything stays finite.  With `unimix == 0` a -inf logit in `post` is
+  0 * -inf in the definition: both paths return NaN for that row's dyn, rep and
+  rep_ent (dyn_ent stays finite) and for post's gradient in that group (the
+  kernels: both gradients over the whole row); one in `prior` alone makes dyn
+  and rep +inf and dyn_ent NaN."""
+  _check_pair('rssm_kl', post, prior)
+  unimix = _check_unimix('rssm_kl', unimix)
+  free_nats = float(free_nats)
+  if not free_nats >= 0.0:
+    raise ValueError(f'rssm_kl: free_nats = {free_nats}, needs >= 0 (0: no maximum)')
+  rows = _rows_of(post)
+  if _kl_path(fused, rows, *post.shape[-2:]) and rows > 0:
+    dyn, rep, dyn_ent, rep_ent = _FusedRssmKL.apply(post, prior, unimix, free_nats)
+    return {'dyn': dyn, 'rep': rep, 'dyn_ent': dyn_ent, 'rep_ent': rep_ent}
+  dist = lambda logits: _onehot_logits(logits, unimix)
+  dyn = _composed_kl(dist(post.detach()), dist(prior))
+  rep = _composed_kl(dist(post), dist(prior.detach()))
+  if free_nats:
+    floor = torch.full((), free_nats, dtype=torch.float32, device=post.device)
+    dyn = torch.maximum(dyn, floor)
+    rep = torch.maximum(rep, floor)
+  with torch.no_grad():
+    dyn_ent = _composed_entropy(dist(prior))
+    rep_ent = _composed_entropy(dist(post))
+  return {'dyn': dyn, 'rep': rep, 'dyn_ent': dyn_ent, 'rep_ent': rep_ent}

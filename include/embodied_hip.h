@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports (122 functions). */
+ * it exports (125 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -43,7 +43,8 @@ extern "C" {
  * Still 5: + emb_normalize, emb_normalize_launches, emb_ppo_targets,
  * emb_ppo_targets_launches, emb_scan_lambda_cont, emb_dreamer_targets,
  * emb_dreamer_targets_launches, emb_twohot_stats, emb_twohot_loss,
- * emb_twohot_grad, emb_twohot_launches (additions only).                       */
+ * emb_twohot_grad, emb_twohot_launches, emb_onehot_kl, emb_onehot_kl_grad,
+ * emb_onehot_kl_launches (additions only).                                     */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -668,6 +669,49 @@ int32_t emb_twohot_grad(const void* logits, int32_t dtype, int64_t rows, int64_t
 /* Kernel launches the three entry points above have issued in this process,
  * counted where the kernels are launched.                                      */
 int32_t emb_twohot_launches(int64_t* count);
+
+/* ---- the RSSM's KL pair over one-hot latents, float32 arithmetic on device --
+ * DreamerV3's world-model loss, RSSM.loss (dreamerv3/rssm.py:123-132), over
+ * _dist = Agg(OneHot(logits, unimix), 1, sum) (dreamerv3/rssm.py:173-176,
+ * embodied/jax/outs.py:40-76 Agg, embodied/jax/outs.py:208-263 Categorical and
+ * OneHot).  `post` and `prior` are (rows, stoch, classes) contiguous on device,
+ * dtype EMB_F32 or EMB_BF16 (bfloat16 is widened in registers; the reference
+ * computes in float32, outs.py:211); kl, ent_post, ent_prior, dyn, rep, g_rep,
+ * g_dyn: `rows` float32 on device.  Per group of `classes` logits
+ *   p = (1 - unimix) * softmax(post) + unimix / classes       (outs.py:212-216)
+ *   q = the same of prior;  unimix == 0: p = softmax(post), log p = log_softmax
+ * and per row, summed over the stoch groups in one fixed order,
+ *   kl = sum p (log p - log q)                                (outs.py:236-240)
+ *   ent_post = -sum p log p, ent_prior = -sum q log q         (outs.py:230-234)
+ * (p sums to 1 up to rounding, so the reference's second softmax over log p is
+ * the identity and is not repeated).  One kernel launch each:
+ *   emb_onehot_kl       rssm.py:125-132: one read of post and prior.  dyn and
+ *                       rep have the same forward value (sg only routes
+ *                       gradients): both receive max(kl, free_nats), or kl where
+ *                       free_nats == 0 (rssm.py:127); either may be NULL.
+ *   emb_onehot_kl_grad  the gradients of that pair in the logits' dtype:
+ *                         grad_post  = g_rep * f * d kl / d post
+ *                         grad_prior = g_dyn * f * d kl / d prior
+ *                       f the gradient of rssm.py:128-129's maximum from the
+ *                       saved `kl`: 1 where kl > free_nats, 0 where kl <
+ *                       free_nats, 1/2 at equality (jnp.maximum's), NaN for a NaN
+ *                       kl; free_nats == 0: 1.  grad_post or grad_prior may be
+ *                       NULL: that side is not written and its g not read.
+ * No atomics: the same bits run to run.
+ * EMB_ERR_INVALID before any launch: an unknown dtype, rows < 0, stoch < 1,
+ * classes outside 1 .. 256, more than 2^31 - 1 logits, unimix outside [0, 1),
+ * free_nats < 0, and with rows > 0 a NULL required pointer (for the gradient:
+ * both outputs NULL, or an output without its g).  rows = 0: EMB_OK, nothing
+ * is launched.                                                                 */
+int32_t emb_onehot_kl(const void* post, const void* prior, int32_t dtype, int64_t rows, int64_t stoch,
+                      int64_t classes, float unimix, float free_nats, void* kl, void* ent_post, void* ent_prior,
+                      void* dyn, void* rep, void* stream);
+int32_t emb_onehot_kl_grad(const void* post, const void* prior, int32_t dtype, int64_t rows, int64_t stoch,
+                           int64_t classes, float unimix, float free_nats, const void* kl, const void* g_rep,
+                           const void* g_dyn, void* grad_post, void* grad_prior, void* stream);
+/* Kernel launches the two entry points above have issued in this process,
+ * counted where the kernels are launched.                                      */
+int32_t emb_onehot_kl_launches(int64_t* count);
 
 /* ----------------------------------------------------------- collectives --
  * The two exchange steps of the sharded path on RCCL directly (xGMI inside one
