@@ -17,6 +17,8 @@ from embodied_amd import normalize as normlib
 from embodied_amd import scans
 from embodied_amd.scans import dreamer_targets, lambda_return_cont      # every test here fails without the feature
 from tests import dreamer_target_cases as cases
+# dreamerv3/agent.py:401-405,482-490 in float64, for inputs that are not in the fixture
+from tests.target_reference import lambda_cont64 as _reference_lambda_cont
 
 pytestmark = pytest.mark.gpu
 GOLDEN = pathlib.Path(__file__).parent / 'golden' / 'dreamer_targets.npz'
@@ -121,18 +123,6 @@ def test_lambda_return_cont_against_the_fixture(golden, case):
       boot = boot * np.float32(cases.NORM['limit']) + np.float32(0)
     ret = lambda_return_cont(_cuda(inp['rew']), _cuda(inp['con']), _cuda(boot), disc, cases.PARAMS['lam'])
     np.testing.assert_allclose(ret.cpu().numpy(), golden[f'ret_{cases.tag(case)}'][step], rtol=RTOL, atol=ATOL)
-
-
-def _reference_lambda_cont(rew, con, boot, disc, lam):
-  """dreamerv3/agent.py:401-405,482-490 in float64, for inputs that are not in
-  the fixture."""
-  rew, con, boot = (np.asarray(x, np.float64) for x in (rew, con, boot))
-  live = (1 - (1 - con))[:, 1:] * disc
-  interm = rew[:, 1:] + (1 - lam) * live * boot[:, 1:]
-  rets = [boot[:, -1]]
-  for t in reversed(range(live.shape[1])):
-    rets.append(interm[:, t] + live[:, t] * lam * rets[-1])
-  return np.stack(list(reversed(rets))[:-1], 1)
 
 
 @pytest.mark.parametrize('shape', [(3, 5), (7, 2), (5, 257), (1, 1030)])
