@@ -28,7 +28,9 @@ device's time.
 The last lines name the shapes at which the kernels' median is below the
 composed one, and those where it is not: what `outs._kl_path` is set from.
 The accuracy file holds, per shape, dtype and unimix, the worst error of both
-paths as a share of the bars of tests/test_gpu_rssm_kl.py.
+paths as a share of the bars of tests/test_gpu_rssm_kl.py: the shapes of that
+test, then those of the sweep over every segment width
+(tests/rssm_kl_sweep_cases.py).
 Needs a GPU: there is no CPU fallback and no figure without one.
 """
 import argparse
@@ -71,14 +73,18 @@ def kernel_calls(post, prior, g_dyn, g_rep):
 
 def accuracy(outs, lines):
   from tests import rssm_kl_cases as cases
+  from tests import rssm_kl_sweep_cases as sweep
   lines += ['# tools/bench_rssm_kl.py: worst error against float64 (tests.rssm_kl_cases.reference64) as a share of the bars',
             '# forward: |got - want| / (1e-5 + 1e-5 |want|) over dyn, rep and both entropies, free_nats 1 and 0;',
             '# gradient: |got - want| / (1e-5 |g| (1 + |want|)) per element (bf16: + 2^-8 |want|); rows 37, logit scales '
             + ', '.join(f'{s:g}' for s in cases.SCALES),
             '# unimix 0: gradients at scales 0.1 and 1 only (the float32 definition misses the bar beyond)',
+            '# shapes: tests.rssm_kl_cases.FUSED_SHAPES, then every (stoch, classes) of tests.rssm_kl_sweep_cases, rung by rung',
             f'# {"shape":<12}{"dtype":<7}{"unimix":<8}{"fused fwd":<12}{"fused grad":<12}{"composed fwd":<14}composed grad']
   worst_all = {True: [0.0, 0.0], False: [0.0, 0.0]}
-  for stoch, classes in cases.FUSED_SHAPES:
+  shapes = list(cases.FUSED_SHAPES)
+  shapes += [shape for shape in sweep.all_shapes() if shape not in shapes]
+  for stoch, classes in shapes:
     for kind in ('f32', 'bf16'):
       for unimix in cases.UNIMIX:
         worst = {True: [0.0, 0.0], False: [0.0, 0.0]}
