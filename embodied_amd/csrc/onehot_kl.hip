@@ -19,6 +19,7 @@
 // then one butterfly across the segments.  No atomics, no traffic between
 // waves: the same bits run to run.
 #include "onehot_kl.h"
+#include "onehot_segment.h"
 
 #include <atomic>
 
@@ -33,90 +34,9 @@ constexpr int kWaves = 4;                         // rows per workgroup at a tim
 constexpr int kThreads = kWave * kWaves;
 constexpr int kMaxBlocks = 2048;                  // 8 workgroups of 4 waves on each of 256 CUs; more rows: grid stride
 
-using bf16_t = uint16_t;                          // the storage; arithmetic is float32
-
-__device__ __forceinline__ float load(const float* x, int64_t i) { return x[i]; }
-__device__ __forceinline__ float load(const bf16_t* x, int64_t i) {
-  return __uint_as_float(static_cast<uint32_t>(x[i]) << 16);
-}
-__device__ __forceinline__ void store(float* x, int64_t i, float v) { x[i] = v; }
-__device__ __forceinline__ void store(bf16_t* x, int64_t i, float v) {
-  const uint32_t u = __float_as_uint(v);
-  // round to nearest even; a NaN keeps a set mantissa bit
-  x[i] = v != v ? static_cast<bf16_t>((u >> 16) | 0x40u) : static_cast<bf16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
-// Butterflies over the W lanes of a segment: every lane of it ends with the same bits.
-template <int W>
-__device__ __forceinline__ float seg_max(float v) {
-#pragma unroll
-  for (int o = W / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
-  return v;
-}
-template <int W>
-__device__ __forceinline__ float seg_sum(float v) {
-#pragma unroll
-  for (int o = W / 2; o > 0; o >>= 1) v = v + __shfl_xor(v, o, kWave);
-  return v;
-}
-// ... and over the 64 / W segments of the wave, of a value every lane of a segment shares.
-template <int W>
-__device__ __forceinline__ float across_sum(float v) {
-#pragma unroll
-  for (int o = kWave / 2; o >= W; o >>= 1) v = v + __shfl_xor(v, o, kWave);
-  return v;
-}
-
-// One group of one side, lane sl of its segment holding elements sl, sl + W, ...:
-// sm = softmax(x) (outs.py:213), prob and logp the distribution the reference's
-// kl and entropy work on -- outs.py:214-216 with unimix, the logits themselves
-// (log_softmax in the log domain, finite for an underflowed class) without.
-// After the mix the probabilities sum to 1 up to rounding, so the second softmax
-// / log_softmax of outs.py:231-232, 237-239 is the identity and is not repeated.
-// Lanes past `classes` hold zeros; a segment past `stoch` (!live) works on zeros
-// and reads nothing.
-template <int NPER>
-struct Side {
-  float sm[NPER], prob[NPER], logp[NPER];
-};
-
-template <typename T, int W, int NPER>
-__device__ __forceinline__ Side<NPER> side(const T* x, bool live, int sl, int classes, float unimix, float keep,
-                                           float uni) {
-  Side<NPER> s;
-  float m = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < NPER; ++j) {
-    const int i = sl + W * j;
-    s.logp[j] = i < classes ? (live ? load(x, i) : 0.f) : -INFINITY;
-    m = fmaxf(m, s.logp[j]);
-  }
-  m = seg_max<W>(m);
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < NPER; ++j) {
-    const int i = sl + W * j;
-    s.sm[j] = i < classes ? expf(s.logp[j] - m) : 0.f;
-    sum = sum + s.sm[j];
-  }
-  sum = seg_sum<W>(sum);
-  const float lsum = logf(sum);
-#pragma unroll
-  for (int j = 0; j < NPER; ++j) {
-    const bool ok = sl + W * j < classes;
-    const float sm = s.sm[j] / sum;
-    s.sm[j] = ok ? sm : 0.f;
-    if (unimix != 0.f) {
-      const float prob = keep * sm + uni;
-      s.prob[j] = ok ? prob : 0.f;
-      s.logp[j] = ok ? logf(prob) : 0.f;
-    } else {
-      s.prob[j] = s.sm[j];
-      s.logp[j] = ok ? (s.logp[j] - m) - lsum : 0.f;
-    }
-  }
-  return s;
-}
+// bf16_t, load / store, seg_max / seg_sum / across_sum, Side and side(): onehot_segment.h
+using namespace segment;
+static_assert(kWave == kLanes, "the segment helpers shuffle over one wave64");
 
 template <typename T, int W, int NPER>
 __global__ __launch_bounds__(kThreads) void onehot_kl_kernel(const T* __restrict__ post, const T* __restrict__ prior,

@@ -1,7 +1,9 @@
 """Output heads on device: the `symexp_twohot` head of DreamerV3's reward and
 value networks (embodied/jax/heads.py:132-144, embodied/jax/outs.py:273-330),
-and the one-hot latents' KL pair of its world model (`OneHot`, `rssm_kl`:
-dreamerv3/rssm.py:123-132, embodied/jax/outs.py:40-76, 208-263).
+the one-hot latents' KL pair of its world model (`OneHot`, `rssm_kl`:
+dreamerv3/rssm.py:123-132, embodied/jax/outs.py:40-76, 208-263), and the
+actor's discrete policy head and loss (`Categorical`, `policy_loss`:
+dreamerv3/agent.py:411-415, embodied/jax/outs.py:208-240).
 
 It sits on both sides of `scans.dreamer_targets`: that function's `pred`
 argument is `value.pred()` / `slowvalue.pred()` and its `tar_padded` result goes
@@ -564,3 +566,278 @@ def rssm_kl(post, prior, unimix=0.01, free_nats=1.0, fused=None):
     dyn_ent = _composed_entropy(dist(prior))
     rep_ent = _composed_entropy(dist(post))
   return {'dyn': dyn, 'rep': rep, 'dyn_ent': dyn_ent, 'rep_ent': rep_ent}
+
+
+# ---- Categorical: the actor's discrete policy, its logp, entropy and loss ----
+
+# What the kernels take: a group of at most 256 classes stays in one wave's
+# registers, indices are 32-bit.  Structural, not a crossover: the fused median
+# is below the composed one at all 48 rows of profiles/policy_loss_bench.txt (N
+# 1024 and 16 384, T 16, classes 6, 18 and 256, one group and four, float32 and
+# bfloat16, forward and forward + backward) -- (16384, 16, 4, 256) f32: forward
+# 488.9 us against 4436.5, forward + backward 1710.5 against 8926.0; the closest,
+# (16384, 16, 6) bf16: 75.3 / 100.4 and 195.6 / 259.0 -- so no size constant sits
+# beside `_policy_path`.
+POLICY_MAX_CLASSES = 256
+POLICY_MAX_LOGITS = 2 ** 31 - 1
+
+
+def policy_loss_launches():
+  """Kernel launches `emb_policy_loss` and `emb_policy_loss_grad` have issued in
+  this process."""
+  count = C.c_int64(0)
+  api.emb_policy_loss_launches(C.byref(count))
+  return count.value
+
+
+def _policy_path(fused, rows, groups, classes):
+  """True: the kernels, False: the composed path (`policy_loss` says when);
+  `rows` counts the logits' rows, a dropped step's included.  The kernels' median
+  was below the composed path's at every shape, dtype and piece measured
+  (profiles/policy_loss_bench.txt), so `fused=None` takes them wherever they fit."""
+  fits = 1 <= classes <= POLICY_MAX_CLASSES and groups >= 1 and rows * groups * classes <= POLICY_MAX_LOGITS
+  if fused and not 1 <= classes <= POLICY_MAX_CLASSES:
+    raise ValueError(
+        f'Categorical(fused=True): {classes} classes, the kernels keep a group of at most {POLICY_MAX_CLASSES} in '
+        'one wave\'s registers (fused=None or False composes it)')
+  if fused and not fits:
+    raise ValueError(
+        f'Categorical(fused=True): {rows} x {groups} x {classes} logits, the kernels index 1 .. 2^31 - 1 '
+        '(fused=None or False composes it)')
+  if fused is None:
+    return fits
+  return bool(fused)
+
+
+def _check_device(logits):
+  if not (torch.is_tensor(logits) and logits.is_cuda):
+    raise RuntimeError('embodied_amd.outs runs as HIP kernels: pass CUDA tensors (no CPU fallback)')
+
+
+def _check_categorical(who, logits, dims):
+  _check_device(logits)
+  if logits.dtype not in _DTYPES:
+    raise TypeError(f'{who}: logits must be float32 or bfloat16, got {logits.dtype}')
+  if dims not in (0, 1):
+    raise ValueError(f'{who}: dims = {dims!r}, needs 0 (..., classes) or 1 (..., groups, classes); '
+                     'flatten more action dimensions into the groups')
+  if logits.dim() < 1 + dims or logits.shape[-1] < 1:
+    raise ValueError(f'{who}: logits of shape {tuple(logits.shape)}, needs '
+                     f'{"(..., groups, classes)" if dims else "(..., classes)"}')
+
+
+def _actions(who, act, logits, dims):
+  """`act` as int32 on the logits' device, shaped as the logits without their
+  classes.  Values stay what they are: the one-hot is a comparison, an action
+  outside [0, classes) matches no class."""
+  want = logits.shape[:-1]
+  if not torch.is_tensor(act):
+    act = torch.as_tensor(np.asarray(act))
+  if act.dtype.is_floating_point or act.dtype in (torch.bool, torch.complex64, torch.complex128):
+    raise TypeError(f'{who}: actions must be integers, got {act.dtype}')
+  if act.shape != want:
+    raise ValueError(f'{who}: actions of shape {tuple(act.shape)}, the logits need {tuple(want)}')
+  act = act.detach().to(logits.device)
+  if act.dtype != torch.int32:
+    if act.dtype == torch.int64:        # what does not fit int32 is out of range before and after
+      act = act.clamp(-1, logits.shape[-1])
+    act = act.to(torch.int32)
+  return act.contiguous()
+
+
+def _composed_logp(logits, act, dims):
+  """outs.py:226-228 under `Agg.logp` (outs.py:63-64): `logits` is what
+  `Categorical.__init__` keeps, `act` int32.  jax.nn.one_hot as a comparison
+  with arange: a row of zeros for an action outside [0, classes)."""
+  classes = logits.shape[-1]
+  onehot = (act[..., None] == torch.arange(classes, dtype=torch.int32, device=act.device)).to(torch.float32)
+  logp = (torch.log_softmax(logits, -1) * onehot).sum(-1)
+  return logp.sum(-1) if dims else logp
+
+
+def _composed_cat_entropy(logits, dims):
+  """outs.py:230-234 under `Agg.entropy` (outs.py:69-71)."""
+  logprob = torch.log_softmax(logits, -1)
+  prob = torch.softmax(logits, -1)
+  entropy = -(prob * logprob).sum(-1)
+  return entropy.sum(-1) if dims else entropy
+
+
+class _FusedPolicy(torch.autograd.Function):
+  """(loss, logpi, ent), each (N * (T - drop),) float32, on the kernels: one
+  launch forward, one backward.  Only `loss` carries a gradient, to the logits."""
+
+  @staticmethod
+  def forward(ctx, logits, act, adv, weight, stride, geometry, unimix, actent):
+    n, t, drop, groups, classes = geometry
+    x = logits.detach().contiguous()
+    dtype = _DTYPES[logits.dtype]
+    loss, logpi, ent = _lib.empty((3, n * (t - drop)), torch.float32, x.device).unbind(0)
+    address = lambda tensor: None if tensor is None else tensor.data_ptr()
+    api.emb_policy_loss(
+        x.data_ptr(), address(act), dtype, n, t, drop, groups, classes, unimix, actent, address(adv), address(weight),
+        stride, loss.data_ptr(), logpi.data_ptr(), ent.data_ptr(), _lib.raw_stream(x.device))
+    ctx.saved = (x, act, adv, weight, stride, geometry, unimix, actent, dtype, logits.shape)
+    ctx.set_materialize_grads(False)
+    ctx.mark_non_differentiable(logpi, ent)
+    return loss, logpi, ent
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout, _logpi, _ent):
+    if gout is None:
+      return (None,) * 8
+    x, act, adv, weight, stride, geometry, unimix, actent, dtype, shape = ctx.saved
+    n, t, drop, groups, classes = geometry
+    gout = gout.to(torch.float32).contiguous()
+    grad = torch.empty_like(x)
+    address = lambda tensor: None if tensor is None else tensor.data_ptr()
+    api.emb_policy_loss_grad(
+        x.data_ptr(), address(act), dtype, n, t, drop, groups, classes, unimix, actent, address(adv), address(weight),
+        stride, gout.data_ptr(), grad.data_ptr(), _lib.raw_stream(x.device))
+    return (grad.view(shape),) + (None,) * 7
+
+
+class Categorical:
+  """The reference's `Agg(Categorical(logits, unimix), dims, sum)` (heads.py:90-91,
+  101-110, outs.py:40-76, 208-240), the discrete policy head, over a CUDA tensor
+  of float32 or bfloat16:
+
+    dims=0   logits (..., classes), actions (...)
+    dims=1   logits (..., groups, classes), actions (..., groups), `logp` and
+             `entropy` summed over the groups; more action dimensions are
+             flattened into the groups by the caller
+
+  `.logp(act)` and `.entropy()` are (...) float32 and differentiable once with
+  respect to the logits (the entropy is part of the actor's loss, agent.py:412-414);
+  `.pred()` is the argmax (composed torch ops).  `.minent = 0` and
+  `.maxent = log(classes) * groups` are what agent.py:440-442 reads.  `sample` is
+  not provided.  An action outside [0, classes) has log-probability 0, as the row
+  of zeros `jax.nn.one_hot` gives it; it is never used as an address.
+
+  Two paths, as `OneHot`: composed restates the reference line by line in torch
+  (the definition, every size); fused is `emb_policy_loss` /
+  `emb_policy_loss_grad`, classes <= 256, one launch per call and one per
+  backward.  `fused=None` takes the kernels where they fit, True / False force a
+  path (True raises where they do not fit, and says why).  No rows: the composed
+  path, nothing is launched.  `policy_loss` documents the arithmetic and the
+  non-finite logits."""
+
+  def __init__(self, logits, unimix=0.0, dims=0, fused=None):
+    _check_categorical('Categorical', logits, dims)
+    self.logits = logits
+    self.unimix = _check_unimix('Categorical', unimix)
+    self.dims = dims
+    self._lead = logits.shape[:-1 - dims]
+    self._groups = logits.shape[-2] if dims else 1
+    self._classes = logits.shape[-1]
+    self._rows = int(np.prod(self._lead, dtype=np.int64))
+    self.fused = _policy_path(fused, self._rows, self._groups, self._classes) and self._rows > 0 and self._groups > 0
+    self.minent = 0.0
+    self.maxent = float(np.log(self._classes)) * self._groups
+
+  def _launch(self, act, actent):
+    geometry = (self._rows, 1, 0, self._groups, self._classes)
+    return _FusedPolicy.apply(self.logits, act, None, None, 1, geometry, self.unimix, actent)[0].view(self._lead)
+
+  def pred(self):
+    """outs.py:219-220: the argmax over the classes, int64, (...) or (..., groups)."""
+    return torch.argmax(_onehot_logits(self.logits.detach(), self.unimix), -1)
+
+  def logp(self, act):
+    """(...) float32: the log-probability of `act` (int32 or int64; a constant)."""
+    act = _actions('Categorical.logp', act, self.logits, self.dims)
+    if self.fused:
+      return -self._launch(act, 0.0)              # the launch's loss with adv = weight = 1, actent = 0 is -logp
+    return _composed_logp(_onehot_logits(self.logits, self.unimix), act, self.dims)
+
+  def entropy(self):
+    """(...) float32."""
+    if self.fused:
+      return self._launch(None, -1.0)             # no action and actent = -1: the launch's loss is the entropy
+    return _composed_cat_entropy(_onehot_logits(self.logits, self.unimix), self.dims)
+
+
+def policy_loss(logits, act, adv, weight, actent=3e-4, unimix=0.0, dims=0, drop_last=True, fused=None):
+  """The actor's loss of `imag_loss` (agent.py:411-415) for one action key:
+
+      logpi = policy.logp(sg(act))[:, :-1]
+      ent   = policy.entropy()[:, :-1]
+      loss  = sg(weight[:, :-1]) * -(logpi * sg(adv) + actent * ent)
+
+  with policy = `Categorical(logits, unimix, dims)`, as a dict of three float32
+  tensors.  `loss` is differentiable once with respect to the logits and to
+  nothing else: `adv` and `weight` are constants, the reference's `sg`.  `logpi`
+  and `ent` carry no gradient; they are for `metrics['ent/...']`
+  (agent.py:438-442).
+
+  `logits` is (N.., T, [groups,] classes) and `act` (N.., T[, groups]) int32 or
+  int64.  With `drop_last` the last step of every sequence is dropped, the
+  reference's `[:, :-1]`: the outputs and `adv` are (N.., T - 1), and `weight` is
+  (N.., T) as `scans.dreamer_targets` returns it or (N.., T - 1).  Without it all
+  three are the leading shape of the logits, whatever its rank.  The kernels read
+  the kept rows in place: the logits are neither sliced nor copied and a dropped
+  step is not read.
+
+  A dict of actions needs no fused sum of heads: the loss is linear in `logpi`
+  and `ent`, so the reference's sum over action keys (agent.py:411-414) is the sum
+  of one `policy_loss` per key.
+
+  Two paths, as `Categorical`.  On the kernels that is ONE launch forward and ONE
+  backward.  No output rows (N = 0, or T = 1 with `drop_last`): nothing is
+  launched and the gradient is zeros.
+
+  Per group the reference mixes, takes the log, and then runs softmax and
+  log_softmax over that log again (outs.py:212-216, 228, 231-232).  The composed
+  path repeats that; the kernels do not: after the mix the probabilities sum to 1
+  up to rounding, so the second pass is the identity.  With `unimix == 0` both
+  work in the log domain (`log_softmax`), finite for a class whose probability
+  underflows.
+
+  Non-finite logits.  A NaN or +inf logit, or a group of -inf, in a kept step
+  makes that output row's `loss`, `logpi` and `ent` NaN on both paths and touches
+  no other row.  Its gradient: on the kernels the whole row's is NaN; composed is
+  the definition, NaN in the poisoned group and whatever autograd leaves in the
+  row's other groups.  The same values in a dropped step touch nothing: every
+  output has the bits of the clean run and that step's gradient is zeros.  With
+  `unimix > 0` a single -inf logit is a class of probability unimix / classes and
+  everything stays finite.  With `unimix == 0` it is 0 * -inf in the definition's
+  entropy and in its product with the one-hot: both paths return NaN for that
+  row's three outputs."""
+  _check_categorical('policy_loss', logits, dims)
+  unimix = _check_unimix('policy_loss', unimix)
+  actent = float(actent)
+  if not np.isfinite(actent):
+    raise ValueError(f'policy_loss: actent = {actent}, needs a finite value')
+  lead = logits.shape[:-1 - dims]
+  groups, classes = (logits.shape[-2] if dims else 1), logits.shape[-1]
+  drop = 1 if drop_last else 0
+  if drop and not lead:
+    raise ValueError(f'policy_loss: drop_last needs a time axis, logits of shape {tuple(logits.shape)}')
+  n, t = (int(np.prod(lead[:-1], dtype=np.int64)), lead[-1]) if drop else (int(np.prod(lead, dtype=np.int64)), 1)
+  kept = max(t - drop, 0)
+  out_shape = (*lead[:-1], kept) if drop else tuple(lead)
+  act = _actions('policy_loss', act, logits, dims)
+
+  def constant(name, value, shapes):
+    if not torch.is_tensor(value):
+      value = torch.as_tensor(np.asarray(value, np.float32))
+    if tuple(value.shape) not in shapes:
+      raise ValueError(f'policy_loss: {name} of shape {tuple(value.shape)}, needs ' +
+                       ' or '.join(str(tuple(s)) for s in shapes))
+    return value.detach().to(device=logits.device, dtype=torch.float32).contiguous()
+
+  adv = constant('adv', adv, (out_shape,))
+  weight = constant('weight', weight, (out_shape, tuple(lead)))
+  if _policy_path(fused, n * t, groups, classes) and n * kept > 0 and groups > 0:
+    stride = weight.shape[-1] if drop else 1
+    loss, logpi, ent = _FusedPolicy.apply(logits, act, adv, weight, stride, (n, t, drop, groups, classes), unimix, actent)
+    return {'loss': loss.view(out_shape), 'logpi': logpi.view(out_shape), 'ent': ent.view(out_shape)}
+  if drop:      # the reference's [:, :-1], taken before the arithmetic instead of after: a dropped step takes no part
+    axis = len(lead) - 1
+    logits, act, weight = logits.narrow(axis, 0, kept), act.narrow(axis, 0, kept), weight[..., :kept]
+  dist = _onehot_logits(logits, unimix)
+  logpi = _composed_logp(dist, act, dims)
+  ent = _composed_cat_entropy(dist, dims)
+  loss = weight * -(logpi * adv + actent * ent)
+  return {'loss': loss, 'logpi': logpi.detach(), 'ent': ent.detach()}

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports (125 functions). */
+ * it exports (128 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -44,7 +44,8 @@ extern "C" {
  * emb_ppo_targets_launches, emb_scan_lambda_cont, emb_dreamer_targets,
  * emb_dreamer_targets_launches, emb_twohot_stats, emb_twohot_loss,
  * emb_twohot_grad, emb_twohot_launches, emb_onehot_kl, emb_onehot_kl_grad,
- * emb_onehot_kl_launches (additions only).                                     */
+ * emb_onehot_kl_launches, emb_policy_loss, emb_policy_loss_grad,
+ * emb_policy_loss_launches (additions only).                                  */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -712,6 +713,56 @@ int32_t emb_onehot_kl_grad(const void* post, const void* prior, int32_t dtype, i
 /* Kernel launches the two entry points above have issued in this process,
  * counted where the kernels are launched.                                      */
 int32_t emb_onehot_kl_launches(int64_t* count);
+
+/* ---- the actor's loss over a categorical policy, float32 arithmetic on device
+ * DreamerV3's imag_loss, dreamerv3/agent.py:411-415:
+ *   logpi = sum_k policy[k].logp(sg(act[k]))[:, :-1]
+ *   ents  = policy[k].entropy()[:, :-1]
+ *   policy_loss = sg(weight[:, :-1]) * -(logpi * sg(adv_normed) + actent * ents)
+ * for one action key (the loss is linear in logpi and ents: the sum over keys
+ * is the sum of one call per key), policy[k] = Agg(Categorical(logits, unimix),
+ * dims, sum) (embodied/jax/heads.py:90-91, 101-110; embodied/jax/outs.py:40-76
+ * Agg, embodied/jax/outs.py:208-234 Categorical).  `logits` is (N, T, groups,
+ * classes) contiguous on device, dtype EMB_F32 or EMB_BF16 (widened in
+ * registers; the reference computes in float32, outs.py:211); `act` (N, T,
+ * groups) int32 on device, or NULL (no action: logpi = 0 and its gradient 0).
+ * `drop` is 0 or 1, the reference's [:, :-1] taken inside the launch: an output
+ * row r = (n, t), t < T - drop, reads the logits' row n * T + t, and the last step
+ * of every n is not read.  adv, loss, logpi, ent and gout are (N, T - drop)
+ * float32 on device; `weight` is float32 read at n * weight_stride + t, so (N, T)
+ * as emb_dreamer_targets writes it (stride T) and (N, T - drop) both go.  adv
+ * and weight may be NULL: 1.  Per group of `classes` logits
+ *   p = (1 - unimix) * softmax(x) + unimix / classes, logp = log p (outs.py:212-216)
+ *   unimix == 0: p = softmax(x), logp = log_softmax(x), in the log domain
+ * and per output row, summed over the groups in one fixed order,
+ *   logpi = sum_g logp[g, act[g]]      (outs.py:226-228, 63-64; the action is
+ *           compared with the class index, never an address: one outside
+ *           [0, classes) adds 0, as jax.nn.one_hot)
+ *   ent   = sum_g -sum_k p_k logp_k    (outs.py:230-234, 69-71)
+ *   loss  = weight * -(logpi * adv + actent * ent)            (agent.py:413-414)
+ * One kernel launch each:
+ *   emb_policy_loss       one read of the logits; `loss` may be NULL (not written).
+ *   emb_policy_loss_grad  grad (N, T, groups, classes) in the logits' dtype =
+ *                         gout * d loss / d logits, the closed form from one more
+ *                         read (nothing the forward wrote is used); the rows of
+ *                         a dropped step are written as zeros; a row with a NaN
+ *                         or +inf logit or a group of -inf is NaN throughout.
+ * No atomics: the same bits run to run.
+ * EMB_ERR_INVALID before any launch: an unknown dtype, N or T < 0, drop not 0 or
+ * 1, groups < 1, classes outside 1 .. 256, more than 2^31 - 1 logits, unimix
+ * outside [0, 1), a non-finite actent, and with work to do a NULL logits, logpi,
+ * ent, gout or grad, or a weight_stride below T - drop.  No output rows (N = 0
+ * or T - drop = 0): emb_policy_loss launches nothing; emb_policy_loss_grad
+ * launches nothing without logits (N * T = 0) and otherwise writes the zeros.  */
+int32_t emb_policy_loss(const void* logits, const void* act, int32_t dtype, int64_t N, int64_t T, int32_t drop,
+                        int64_t groups, int64_t classes, float unimix, float actent, const void* adv,
+                        const void* weight, int64_t weight_stride, void* loss, void* logpi, void* ent, void* stream);
+int32_t emb_policy_loss_grad(const void* logits, const void* act, int32_t dtype, int64_t N, int64_t T, int32_t drop,
+                             int64_t groups, int64_t classes, float unimix, float actent, const void* adv,
+                             const void* weight, int64_t weight_stride, const void* gout, void* grad, void* stream);
+/* Kernel launches the two entry points above have issued in this process,
+ * counted where the kernels are launched.                                      */
+int32_t emb_policy_loss_launches(int64_t* count);
 
 /* ----------------------------------------------------------- collectives --
  * The two exchange steps of the sharded path on RCCL directly (xGMI inside one
