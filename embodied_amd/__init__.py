@@ -36,6 +36,8 @@ from . import outs
 from .outs import TwoHot, symexp_twohot_bins, twohot_launches
 from .outs import OneHot, rssm_kl, onehot_kl_launches
 from .outs import Categorical, policy_loss, policy_loss_launches
+from . import optim
+from .optim import LaProp, optimizer_launches
 from .utils import Counter, LocalClock
 from .distributed import GlobalClock
 # `embodied.clock.*` by name (embodied/core/__init__.py:4-5,11): the two clocks and

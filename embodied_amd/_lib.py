@@ -212,6 +212,11 @@ SIGNATURES = {
     'emb_policy_loss': [p, p, i32, i64, i64, i32, i64, i64, f32, f32, p, p, i64, p, p, p, p],
     'emb_policy_loss_grad': [p, p, i32, i64, i64, i32, i64, i64, f32, f32, p, p, i64, p, p, p],
     'emb_policy_loss_launches': [p],
+    'emb_optim_table': [p, p, p, i64, p, p, i64, p, p, p],
+    'emb_optim_norms': [p, p, i64, p, p],
+    'emb_optim_update': [p, p, i64, p, f32, f32, f32, f32, f32, f32, f32, f32, f32, f32, f32, i32, p],
+    'emb_optim_metrics': [p, i64, i64, p, p],
+    'emb_optim_launches': [p],
     'emb_synth_env_step': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p],
     'emb_synth_env_step_masked': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p, p, i64, i32, p],
     'emb_env_mask_supported': [i64, i32],

@@ -19,10 +19,10 @@ CSRC = HERE / 'csrc'
 OUT = HERE / 'libembodied_hip.so'
 OBJ = HERE / 'build'
 SOURCES = ['movers.hip', 'step.hip', 'scans.hip', 'synth_env.hip', 'direct_comm.hip', 'normalize.hip', 'ppo_targets.hip',
-           'dreamer_targets.hip', 'twohot.hip', 'onehot_kl.hip', 'policy_loss.hip',
+           'dreamer_targets.hip', 'twohot.hip', 'onehot_kl.hip', 'policy_loss.hip', 'optim.hip',
            'replay_abi.cpp', 'index_abi.cpp', 'kernels_abi.cpp', 'env_abi.cpp', 'comm_abi.cpp', 'normalize_abi.cpp',
            'ppo_targets_abi.cpp', 'dreamer_targets_abi.cpp', 'twohot_abi.cpp', 'onehot_kl_abi.cpp',
-           'policy_loss_abi.cpp']
+           'policy_loss_abi.cpp', 'optim_abi.cpp']
 ARCH = 'gfx950'
 # CPython call shim for the hottest entry points (csrc/fastcall.c): plain C,
 # links against nothing; the package falls back to ctypes without it.

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports (128 functions). */
+ * it exports (133 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -45,7 +45,8 @@ extern "C" {
  * emb_dreamer_targets_launches, emb_twohot_stats, emb_twohot_loss,
  * emb_twohot_grad, emb_twohot_launches, emb_onehot_kl, emb_onehot_kl_grad,
  * emb_onehot_kl_launches, emb_policy_loss, emb_policy_loss_grad,
- * emb_policy_loss_launches (additions only).                                  */
+ * emb_policy_loss_launches, emb_optim_table, emb_optim_norms, emb_optim_update,
+ * emb_optim_metrics, emb_optim_launches (additions only).                     */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -763,6 +764,70 @@ int32_t emb_policy_loss_grad(const void* logits, const void* act, int32_t dtype,
 /* Kernel launches the two entry points above have issued in this process,
  * counted where the kernels are launched.                                      */
 int32_t emb_policy_loss_launches(int64_t* count);
+
+/* ---- the learner's optimizer step, float32 arithmetic on device
+ * The reference's chain, dreamerv3/agent.py:342-379, over every parameter tensor
+ * at once:
+ *   clip_by_agc        embodied/jax/opt.py:109-123
+ *   scale_by_rms       embodied/jax/opt.py:126-143
+ *   scale_by_momentum  embodied/jax/opt.py:146-164
+ *   optax.add_decayed_weights, scale_by_learning_rate (agent.py:361-378) and
+ *   optax.apply_updates (opt.py:62),
+ * and the metrics of embodied/jax/opt.py:64-79.  Per tensor, t the number of this
+ * update counted from 1, the caller handing over omb = 1 - beta and c = 1 -
+ * beta^t, each formed in double and rounded once:
+ *   unorm = ||g||2, pnorm = ||p||2                             (opt.py:116-117)
+ *   g1 = g * (1 / maximum(1, unorm / (agc * maximum(pmin, pnorm))))   agc == 0: g
+ *   nu = beta2 * nu + omb2 * (g1 * g1)                         (opt.py:136-137)
+ *   u  = g1 / (sqrt(nu / c2) + eps)                            (opt.py:138-140)
+ *   mu = omb1 * u + beta1 * mu                                 (opt.py:156)
+ *   m  = mu / c1, nesterov: (omb1 * u + beta1 * mu) / c1       (opt.py:157-161)
+ *   upd = (m + wd * p where the tensor decays, else m) * -lr   (agent.py:365, 378)
+ *   p  = p + upd
+ * `maximum` hands a NaN on: one NaN in a tensor's gradient makes its p, nu and mu
+ * NaN throughout; an infinity and no NaN gives the scale 0, g1 = 0 for the finite
+ * elements and NaN for the infinite ones; no other tensor is touched.
+ *
+ * Work is cut into chunks of one tensor each.  emb_optim_table (host only, no
+ * HIP call) writes what the kernels read through two device pointers:
+ *   table   one record of `record_bytes` per tensor, from addrs (tensors, 4) =
+ *           the device addresses of p, g, nu, mu (float32; g bfloat16 with
+ *           EMB_OPTIM_BF16), counts (tensors) elements each, 0 .. 2^31 - 1, and
+ *           flags (tensors) of EMB_OPTIM_BF16 | EMB_OPTIM_DECAY
+ *   chunks  one 8-byte record per chunk (`chunk_capacity` = what `chunks` holds)
+ * Either may be NULL (not written); n_chunks, chunk_size (elements per chunk) and
+ * record_bytes receive their values where not NULL.  The caller copies both to
+ * the device, and the table again whenever an address changes.  A tensor whose
+ * p, g, nu and mu start at the same element offset modulo 4 is read and written
+ * in 16-byte vectors with scalar ragged ends; any other alignment goes scalar.
+ *   emb_optim_norms    launch 1: every chunk's sum g^2 and sum p^2 into `partials`,
+ *                      (4, n_chunks) float32 on device
+ *   emb_optim_update   launch 2: every workgroup sums its tensor's partials in a
+ *                      fixed order, forms the scale and updates its chunk in
+ *                      place; leaves sum upd^2 and sum p_new^2 per chunk behind
+ *   emb_optim_metrics  one launch of one workgroup: out (4,) float32 on device =
+ *                      grad_norm (optax.global_norm of the raw gradients),
+ *                      grad_rms, update_rms, param_rms (embodied/jax/nets.py:120-124
+ *                      over `count` elements; the parameters after the update)
+ * No atomics, and no workgroup waits for another: the same bits run to run.
+ * EMB_ERR_INVALID before any launch: sizes outside their ranges, an address that
+ * is null or not aligned to its element, unknown flags, a chunk map that is too
+ * small, a non-finite lr, a beta outside [0, 1), omb or c outside (0, 1], a
+ * negative or non-finite eps, agc, pmin or wd, and with n_chunks > 0 a NULL
+ * pointer.  n_chunks = 0: norms and update launch nothing.                     */
+#define EMB_OPTIM_BF16 1
+#define EMB_OPTIM_DECAY 2
+int32_t emb_optim_table(const int64_t* addrs, const int64_t* counts, const int32_t* flags, int64_t tensors,
+                        void* table, void* chunks, int64_t chunk_capacity, int64_t* n_chunks, int64_t* chunk_size,
+                        int64_t* record_bytes);
+int32_t emb_optim_norms(const void* table, const void* chunks, int64_t n_chunks, void* partials, void* stream);
+int32_t emb_optim_update(const void* table, const void* chunks, int64_t n_chunks, void* partials, float lr, float beta1,
+                         float omb1, float c1, float beta2, float omb2, float c2, float eps, float agc, float pmin,
+                         float wd, int32_t nesterov, void* stream);
+int32_t emb_optim_metrics(const void* partials, int64_t n_chunks, int64_t count, void* out, void* stream);
+/* Kernel launches the three entry points above have issued in this process,
+ * counted where the kernels are launched.                                      */
+int32_t emb_optim_launches(int64_t* count);
 
 /* ----------------------------------------------------------- collectives --
  * The two exchange steps of the sharded path on RCCL directly (xGMI inside one
