@@ -79,7 +79,10 @@ __global__ __launch_bounds__(kThreads) void policy_loss_kernel(
       if (loss) {                                                  // agent.py:413-414
         const float w = weight ? weight[n * weight_stride + t] : 1.f;
         const float advantage = adv ? adv[row] : 1.f;
-        loss[row] = w * -(row_lp * advantage + actent * row_ent);
+        // -(a + b) as -a - b: the same rounding, and a zero keeps the sign that makes the facade's
+        // two uses exact -- actent = 0: the bits of -logpi; no action, actent = -1: the bits of ent,
+        // +0 included (-(0 + -0) would be -0)
+        loss[row] = w * (-(row_lp * advantage) - actent * row_ent);
       }
     }
   }

@@ -111,7 +111,8 @@ def schedule(lr, warmup, count):
 
 def restate(inp, hyper, specs, dtype=torch.float64):
   """The chain on torch CPU in `dtype` over the float32 inputs: a list over the
-  steps of {'p', 'nu', 'mu': [array per tensor], 'metrics': (4,) array}."""
+  steps (as many as `inp['g']` holds, STEPS in every case of the fixture) of
+  {'p', 'nu', 'mu': [array per tensor], 'metrics': (4,) array}."""
   lr0, agc, wd, nesterov, warmup, _ = hyper
   mask = mask_of(specs)
   p = [torch.from_numpy(x).to(dtype) for x in inp['p']]
@@ -119,7 +120,7 @@ def restate(inp, hyper, specs, dtype=torch.float64):
   mu = [torch.zeros_like(x) for x in p]
   count = float(sum(x.numel() for x in p))
   out = []
-  for step in range(STEPS):
+  for step in range(len(inp['g'])):
     t = step + 1
     lr = schedule(lr0, warmup, step)
     gsq, usq, psq = [], [], []

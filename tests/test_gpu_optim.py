@@ -9,7 +9,12 @@ Bars, against float64 over the same float32 inputs: p, mu and the metrics within
 1e-5 + 1e-5 |want|, nu within 1e-5 |want| (floor: the smallest normal float32).
 The float32 definition sits inside all of them on every list
 (tests/test_optim_host.py prints its ratios), so no case is exempt.
-tools/optim_accuracy.py records the worst ratios in profiles/optim_accuracy.txt."""
+tools/optim_accuracy.py records the worst ratios in profiles/optim_accuracy.txt.
+
+The last tests run the lists of tests/optim_sweep_cases.py, which take each
+kernel's loops past their first iteration (more chunks than workgroups, than a
+workgroup's threads, than the metrics kernel's threads), against `reference64`
+at the same bars."""
 import pathlib
 
 import numpy as np
@@ -18,6 +23,7 @@ import torch
 
 from embodied_amd.optim import LaProp, optimizer_launches        # every test here fails without the feature
 from tests import optim_cases as cases
+from tests import optim_sweep_cases as sweep
 
 pytestmark = pytest.mark.gpu
 GOLDEN = pathlib.Path(__file__).parent / 'golden' / 'optim.npz'
@@ -71,29 +77,39 @@ def _set_grads(params, grads, specs, bf16):
     param.grad = _place(g, s.goff, torch.bfloat16 if bf16 else torch.float32)
 
 
-def _make(case, fused, **kw):
-  c = cases.CASES[case]
-  specs = cases.LISTS[c.list]
-  inp = cases.inputs(case)
+def _make_from(specs, inp, h, fused, **kw):
+  """An optimizer over `specs` with the parameters of `inp` and the hyper-parameters `h`."""
   params = _params(inp, specs)
-  h = c.hyper
   opt = LaProp(params, lr=h.lr, agc=h.agc, wd=h.wd, nesterov=h.nesterov, warmup=h.warmup, fused=fused, **kw)
   assert opt.fused is fused
   return opt, params, inp, specs, h
+
+
+def _make(case, fused, **kw):
+  c = cases.CASES[case]
+  return _make_from(cases.LISTS[c.list], cases.inputs(case), c.hyper, fused, **kw)
 
 
 def _host(t):
   return t.detach().float().cpu().numpy()
 
 
+def _gathered(tensors):
+  """Every tensor on the host, in one copy however many there are."""
+  tensors = [t.detach() for t in tensors]
+  flat = _host(torch.cat([t.reshape(-1) for t in tensors]))
+  ends = np.cumsum([t.numel() for t in tensors])
+  return [part.reshape(tuple(t.shape)) for part, t in zip(np.split(flat, ends[:-1]), tensors)]
+
+
 def _state(opt, params):
-  return {'p': [_host(p) for p in params], 'nu': [_host(opt.state[p]['nu']) for p in params],
-          'mu': [_host(opt.state[p]['mu']) for p in params]}
+  return {'p': _gathered(params), 'nu': _gathered([opt.state[p]['nu'] for p in params]),
+          'mu': _gathered([opt.state[p]['mu'] for p in params])}
 
 
-def _run(case, fused, steps=cases.STEPS):
-  """The per-step states (and metrics) of a case on one path."""
-  opt, params, inp, specs, h = _make(case, fused)
+def _run_from(made, steps):
+  """The per-step states (and metrics) of the optimizer `made` (`_make_from`'s) over `steps` steps."""
+  opt, params, inp, specs, h = made
   out = []
   for step in range(steps):
     _set_grads(params, inp['g'][step], specs, h.bf16)
@@ -105,6 +121,11 @@ def _run(case, fused, steps=cases.STEPS):
     assert m['updates'] == step + 1 and m['param_count'] == sum(x.size for x in inp['p'])
     out.append(state)
   return out
+
+
+def _run(case, fused, steps=cases.STEPS):
+  """The per-step states (and metrics) of a case on one path."""
+  return _run_from(_make(case, fused), steps)
 
 
 def _same_bits(a, b):
@@ -255,3 +276,86 @@ def test_a_non_contiguous_parameter_takes_the_composed_path():
   assert optimizer_launches() == before
   # LaProp's first update of a lone tensor: -lr * sign(g) up to the clipping, here below 1 in size
   assert torch.isfinite(params[1]).all() and (params[1] < 0).all() and float(params[1].abs().max()) <= 1e-2 * 1.001
+
+
+# ---- past the first iteration of the kernels' loops: the lists of tests/optim_sweep_cases.py.  `many` has more
+# chunks than kMaxBlocks workgroups (a workgroup meets a second tensor, in another AGC regime) and than the
+# metrics kernel has threads; `deep` has a tensor of more chunks than a workgroup has threads to sum them with.
+
+SWEEP_PATHS = [pytest.param(case, fused, id=f'{sweep.tag(case)}-{"fused" if fused else "composed"}')
+               for case in sweep.CASES for fused in (True, False)]
+
+
+def _make_sweep(case, fused):
+  name, i = case
+  h = sweep.HYPERS[name][i]
+  return _make_from(sweep.LISTS[name], sweep.inputs(name, h.bf16), h, fused)
+
+
+def _first(name, agc=True):
+  return next(case for case in sweep.CASES if case[0] == name and bool(sweep.HYPERS[name][case[1]].agc) == agc)
+
+
+@pytest.mark.parametrize('case,fused', SWEEP_PATHS)
+def test_sweep_lists_against_float64(case, fused):
+  """Every element of p, nu and mu and the four metrics after every step."""
+  name = case[0]
+  specs = sweep.LISTS[name]
+  assert sweep.chunks(sweep.LISTS['many']) > max(sweep.K['kMaxBlocks'], sweep.K['kMetricThreads'])
+  assert max(-(-int(np.prod(s.shape)) // cases.C) for s in sweep.LISTS['deep']) > sweep.K['kThreads']
+  got_all = _run_from(_make_sweep(case, fused), sweep.STEPS[name])
+  want_all = sweep.reference(case)
+  assert len(got_all) == len(want_all) == sweep.STEPS[name] and len(got_all[0]['p']) == len(specs)
+  worst = sweep.worst_ratios(got_all, want_all)
+  print(f'{sweep.tag(case)} {"fused" if fused else "composed"}, {sweep.chunks(specs)} chunks: ' +
+        ', '.join(f'{k} {v:.3g}' for k, v in worst.items()) + ' of its bar')
+  assert max(worst.values()) <= 1.0, worst
+
+
+@pytest.mark.parametrize('name', ['many', 'deep'])
+def test_sweep_lists_take_two_launches_per_step_and_one_for_the_metrics(name):
+  opt, params, inp, specs, h = _make_sweep(_first(name), True)
+  for step in range(2):
+    _set_grads(params, inp['g'][step], specs, h.bf16)
+    before = optimizer_launches()
+    opt.step()
+    assert optimizer_launches() == before + 2, len(params)
+  opt.metrics()
+  assert optimizer_launches() == before + 3
+  composed, cparams, _, _, _ = _make_sweep(_first(name), False)
+  _set_grads(cparams, inp['g'][0], specs, h.bf16)
+  before = optimizer_launches()
+  composed.step()
+  composed.metrics()
+  assert optimizer_launches() == before
+
+
+@pytest.mark.parametrize('name', ['many', 'deep'])
+def test_sweep_lists_identical_state_gives_identical_bits(name):
+  case = _first(name)
+  a, b = (_run_from(_make_sweep(case, True), sweep.STEPS[name]) for _ in range(2))
+  for x, y in zip(a, b):
+    assert _same_bits(x, y) and np.array_equal(x['metrics'], y['metrics'])
+
+
+@PATHS
+def test_a_nan_gradient_stays_out_of_the_tensor_that_shares_its_workgroup(fused):
+  """`many`: tensor 0 and tensor kMaxBlocks are chunk 0 and chunk kMaxBlocks, the
+  same workgroup's first and second on the kernels.  A NaN in tensor 0's gradient
+  makes its scale NaN; tensor kMaxBlocks, and every other tensor, keeps the bits
+  of the clean run."""
+  case = _first('many')
+  blocks = sweep.BLOCKS
+  clean = _run_from(_make_sweep(case, fused), 1)[-1]
+  opt, params, inp, specs, h = _make_sweep(case, fused)
+  assert h.agc and len(params) > blocks
+  grads = [g.copy() for g in inp['g'][0]]
+  grads[0].reshape(-1)[0] = np.nan
+  _set_grads(params, grads, specs, h.bf16)
+  opt.step()
+  got = _state(opt, params)
+  for key in ('p', 'nu', 'mu'):
+    assert np.isnan(got[key][0]).all(), key
+    for i in range(1, len(specs)):
+      assert np.array_equal(got[key][i].view(np.uint32), clean[key][i].view(np.uint32)), (key, i)
+    assert np.isfinite(got[key][blocks]).all()

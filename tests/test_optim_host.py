@@ -334,3 +334,61 @@ def test_composed_path_is_the_restatement(on_host):
     assert seen == [0, 1, 2, 3]
     saved = opt.state_dict()
     assert saved['param_groups'][0]['updates'] == cases.STEPS and len(saved['state']) == len(params)
+
+
+# ---- the lists past the first iteration of the kernels' loops (tests/optim_sweep_cases.py)
+
+def test_the_sweep_lists_exceed_the_constants_they_are_about():
+  from tests import optim_sweep_cases as sweep
+  k = sweep.K
+  kernel = (ROOT / 'embodied_amd' / 'csrc' / 'optim.hip').read_text()
+  for loop in ('chunk += gridDim.x', 'k += kThreads', 'k += kMetricThreads'):
+    assert loop in kernel, loop
+  many, deep = sweep.LISTS['many'], sweep.LISTS['deep']
+  assert len(many) == 2 * k['kMaxBlocks'] + 3 and all(1 <= int(np.prod(s.shape)) <= 5 for s in many)
+  assert sweep.chunks(many) == len(many) > k['kMaxBlocks'] and sweep.chunks(many) > k['kMetricThreads']
+  assert len(set(cases.mask_of(many))) == 2
+  sizes = [int(np.prod(s.shape)) for s in deep]
+  assert sizes == [sweep.DEEP, 3, sweep.DEEP] and -(-sweep.DEEP // cases.C) == k['kThreads'] + 2 > k['kThreads']
+  assert sweep.DEEP % cases.C == 7                                        # a ragged last chunk
+  assert (deep[2].poff, deep[2].goff) == (1, 1) and deep[0].poff is None  # head = 3 behind the small tensor
+  assert [h.agc > 0 for h in sweep.HYPERS['deep']] == [True, True]
+  assert [h.bf16 for h in sweep.HYPERS['deep']] == [False, True]
+  assert sweep.HYPERS['many'] == cases.COVER and sweep.STEPS == {'many': cases.STEPS, 'deep': 2}
+
+
+def test_tensors_that_share_a_workgroup_differ_in_agc_regime():
+  """From float64 on step 1, at agc = 0.3: tensor i < kMaxBlocks is clipped,
+  tensor i + kMaxBlocks (the same workgroup's next chunk) is not, and the last
+  three have pnorm below pmin."""
+  from tests import optim_sweep_cases as sweep
+  blocks = sweep.BLOCKS
+  agc = cases.COVER[0].agc
+  assert agc == 0.3
+  for bf16 in (False, True):
+    inp = sweep.inputs('many', bf16)
+    unorm = np.array([np.sqrt(np.square(g.astype(np.float64)).sum()) for g in inp['g'][0]])
+    pnorm = np.array([np.sqrt(np.square(p.astype(np.float64)).sum()) for p in inp['p']])
+    factor = 1 / np.maximum(1.0, unorm / (agc * np.maximum(cases.PMIN, pnorm)))
+    assert (factor[:blocks] < 1).all() and factor[:blocks].max() < 0.9
+    assert (factor[blocks:2 * blocks] == 1).all()
+    assert (pnorm[2 * blocks:] < cases.PMIN).all() and (pnorm[:2 * blocks] > cases.PMIN).all()
+    assert len(factor) == 2 * blocks + 3
+
+
+@pytest.mark.parametrize('case', __import__('tests.optim_sweep_cases', fromlist=['CASES']).CASES,
+                         ids=lambda case: f'{case[0]}{case[1]}')
+def test_float32_definition_against_the_bars_on_the_sweep_lists(case):
+  """`restate(..., torch.float32)` on every case of the sweep lists sits inside
+  `ratio` and `ratio_nu` against `reference64`, every element and the metrics."""
+  from tests import optim_sweep_cases as sweep
+  name, i = case
+  h = sweep.HYPERS[name][i]
+  inp = sweep.inputs(name, h.bf16)
+  assert len(inp['g']) == sweep.STEPS[name]
+  want = sweep.reference(case)
+  got = cases.restate(inp, h, sweep.LISTS[name], torch.float32)
+  assert len(want) == len(got) == sweep.STEPS[name]
+  worst = sweep.worst_ratios(got, want)
+  print(f'float32 restated, {sweep.tag(case)}: ' + ', '.join(f'{k} {v:.3g}' for k, v in worst.items()) + ' of its bar')
+  assert max(worst.values()) <= 1.0, worst
