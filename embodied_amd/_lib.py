@@ -217,6 +217,12 @@ SIGNATURES = {
     'emb_optim_update': [p, p, i64, p, f32, f32, f32, f32, f32, f32, f32, f32, f32, f32, f32, i32, p],
     'emb_optim_metrics': [p, i64, i64, p, p],
     'emb_optim_launches': [p],
+    'emb_norm_act': [p, p, p, i32, i64, i64, i32, i32, f32, p, p],
+    'emb_norm_act_grad': [p, p, p, p, i32, i64, i64, i32, i32, f32, p, p, p, p, i64, p],
+    'emb_norm_act_launches': [p],
+    'emb_gru_gate': [p, p, i32, i64, i64, i64, p, p],
+    'emb_gru_gate_grad': [p, p, p, i32, i64, i64, i64, p, p, p],
+    'emb_gru_gate_launches': [p],
     'emb_synth_env_step': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p],
     'emb_synth_env_step_masked': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p, p, i64, i32, p],
     'emb_env_mask_supported': [i64, i32],

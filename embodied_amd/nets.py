@@ -1,0 +1,369 @@
+"""The non-GEMM pieces of DreamerV3's recurrence on device: `Norm` followed by the
+activation (embodied/jax/nets.py:361-399, nets.py:26-39), which follows every
+`Linear`, `BlockLinear` and `Conv2D` of the networks and runs four times inside
+`RSSM._core` (dreamerv3/rssm.py:141-151), and the blocked GRU gate at the end of
+`_core` (dreamerv3/rssm.py:152-159).
+
+They feed what `outs` and `scans` consume: `_core`'s new `deter` goes through
+`_prior` (two more norm + activation pairs, rssm.py:163-165) into the logits of
+`outs.rssm_kl`.
+
+Inputs are torch CUDA tensors, float32 or bfloat16; the kernels' arithmetic is
+float32 and rounds once, at the store.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from ._lib import api
+
+# What the kernels take: a row of at most 16 384 units stays in the registers of
+# one workgroup, indices are 32-bit.  Structural, not a crossover: the fused
+# median is below the composed one at all 36 rows of profiles/rssm_core_bench.txt
+# -- norm (16, 1024) f32: forward 15.7 us against 50.3, forward + backward 56.3
+# against 176.2; (16384, 1024) f32: 24.7 / 139.3 and 101.5 / 539.3; gate (16, 8192,
+# 8) f32: 14.2 / 63.1 and 52.1 / 183.8 -- so no size constant sits beside
+# `_norm_path` or `_gate_path`.
+NORM_ACT_MAX_UNITS = 16384
+NORM_ACT_MAX_ELEMENTS = 2 ** 31 - 1
+GRU_GATE_MAX_ELEMENTS = 2 ** 31 - 1                # of x: rows * 3 * deter
+# csrc/norm_act.h: up to here a wave takes a row, four rows per workgroup; the
+# gradient launch has at most this many workgroups, each leaves one row of partial sums
+_WAVE_UNITS, _MAX_PARTIALS = 1024, 512
+
+IMPLS = {'rms': 0, 'layer': 1}
+ACTS = {'none': 0, 'silu': 1, 'gelu': 2, 'relu': 3}
+_DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
+
+
+def norm_act_launches():
+  """Kernel launches `emb_norm_act` and `emb_norm_act_grad` have issued in this process."""
+  count = C.c_int64(0)
+  api.emb_norm_act_launches(C.byref(count))
+  return count.value
+
+
+def gru_gate_launches():
+  """Kernel launches `emb_gru_gate` and `emb_gru_gate_grad` have issued in this process."""
+  count = C.c_int64(0)
+  api.emb_gru_gate_launches(C.byref(count))
+  return count.value
+
+
+def _norm_path(fused, rows, units):
+  """True: the kernels, False: the composed path (`norm_act` says when).
+  The kernels' median was below the composed path's at every shape, dtype and
+  piece measured (profiles/rssm_core_bench.txt), so `fused=None` takes them
+  wherever they fit: that held, no crossover constant."""
+  fits = 1 <= units <= NORM_ACT_MAX_UNITS and rows * units <= NORM_ACT_MAX_ELEMENTS
+  if fused and not 1 <= units <= NORM_ACT_MAX_UNITS:
+    raise ValueError(
+        f'norm_act(fused=True): {units} units, the kernels keep a row of at most {NORM_ACT_MAX_UNITS} in one '
+        'workgroup\'s registers (fused=None or False composes it)')
+  if fused and not fits:
+    raise ValueError(
+        f'norm_act(fused=True): {rows} x {units} elements, the kernels index at most 2^31 - 1 '
+        '(fused=None or False composes it)')
+  if fused is None:
+    return fits
+  return bool(fused)
+
+
+def _gate_path(fused, rows, deter, blocks):
+  """True: the kernel, False: the composed path (`gru_gate` says when).  As
+  `_norm_path`: below the composed path at all 16 rows of profiles/rssm_core_bench.txt,
+  so wherever it fits."""
+  fits = rows * 3 * deter <= GRU_GATE_MAX_ELEMENTS
+  if fused and not fits:
+    raise ValueError(
+        f'gru_gate(fused=True): {rows} x {3 * deter} elements of x, the kernels index at most 2^31 - 1 '
+        '(fused=None or False composes it)')
+  if fused is None:
+    return fits
+  return bool(fused)
+
+
+def _check_device(who, x):
+  if not (torch.is_tensor(x) and x.is_cuda):
+    raise RuntimeError(f'embodied_amd.nets.{who} runs as HIP kernels: pass CUDA tensors (no CPU fallback)')
+
+
+def _check_param(who, name, value, units, like):
+  if value is None:
+    return None
+  if not torch.is_tensor(value):
+    raise TypeError(f'{who}: {name} must be a float32 tensor, got {type(value).__name__}')
+  if value.dtype != torch.float32:
+    raise TypeError(f'{who}: {name} must be float32 (nets.py:404), got {value.dtype}')
+  if tuple(value.shape) != (units,):
+    raise ValueError(f'{who}: {name} of shape {tuple(value.shape)}, {units} units need ({units},)')
+  if value.device != like.device:
+    raise ValueError(f'{who}: {name} on {value.device}, x on {like.device}')
+  return value
+
+
+def _activation(name, x):
+  """nets.py:26-39 for the four names the kernels know, as jax.nn writes them."""
+  if name == 'none':
+    return x
+  if name == 'silu':
+    return x * torch.sigmoid(x)
+  if name == 'gelu':                     # jax.nn.gelu, approximate=True
+    cdf = 0.5 * (1.0 + torch.tanh(0.7978845608028654 * (x + 0.044715 * (x ** 3))))
+    return x * cdf
+  return torch.maximum(x, torch.zeros((), dtype=x.dtype, device=x.device))
+
+
+def _composed_norm_act(x, scale, shift, impl, act, eps):
+  """nets.py:374-399 and nets.py:26-39 operation by operation: float32 inside the
+  norm, rounded to the dtype of `x`, the activation in that dtype."""
+  dtype = x.dtype
+  x = x.to(torch.float32)
+  if impl == 'rms':
+    mean2 = torch.square(x).mean(-1, keepdim=True)
+    x = x * (torch.rsqrt(mean2 + eps) * (1.0 if scale is None else scale))
+  else:
+    mean = x.mean(-1, keepdim=True)
+    mean2 = torch.square(x).mean(-1, keepdim=True)
+    var = torch.maximum(torch.zeros((), dtype=x.dtype, device=x.device), mean2 - torch.square(mean))
+    x = (x - mean) * (torch.rsqrt(var + eps) * (1.0 if scale is None else scale))
+    if shift is not None:
+      x = x + shift
+  return _activation(act, x.to(dtype))
+
+
+def _partial_floats(rows, units):
+  """float32 values `emb_norm_act_grad` wants for its partial sums (norm_act_partials
+  in csrc/norm_act.h; tests/test_norm_act_host.py holds the two against each other)."""
+  per_block = 4 if units <= _WAVE_UNITS else 1
+  return 2 * min(-(-rows // per_block), _MAX_PARTIALS) * units
+
+
+class _FusedNormAct(torch.autograd.Function):
+  """act(Norm(x)) on the kernels: one launch forward; backward one launch, two
+  with a gradient for `scale` or `shift`."""
+
+  @staticmethod
+  def forward(ctx, x, scale, shift, impl, act, eps):
+    units = x.shape[-1]
+    flat = x.detach().reshape(-1, units).contiguous()
+    out = torch.empty_like(flat)
+    address = lambda tensor: None if tensor is None else tensor.data_ptr()
+    scale = None if scale is None else scale.detach().contiguous()
+    shift = None if shift is None else shift.detach().contiguous()
+    api.emb_norm_act(flat.data_ptr(), address(scale), address(shift), _DTYPES[x.dtype], flat.shape[0], units, impl,
+                     act, eps, out.data_ptr(), _lib.raw_stream(x.device))
+    ctx.saved = (flat, scale, shift, impl, act, eps, x.shape)
+    ctx.set_materialize_grads(False)
+    return out.view(x.shape)
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    if gout is None:
+      return (None,) * 6
+    flat, scale, shift, impl, act, eps, shape = ctx.saved
+    rows, units = flat.shape
+    want_x, want_scale, want_shift = ctx.needs_input_grad[:3]
+    want_shift = want_shift and impl == IMPLS['layer']
+    gout = gout.to(flat.dtype).reshape(rows, units).contiguous()
+    dx = torch.empty_like(flat) if want_x else None
+    dscale = _lib.empty((units,), torch.float32, flat.device) if want_scale else None
+    dshift = _lib.empty((units,), torch.float32, flat.device) if want_shift else None
+    partials, floats = None, 0
+    if want_scale or want_shift:
+      floats = _partial_floats(rows, units)
+      partials = _lib.empty((floats,), torch.float32, flat.device)
+    if dx is None and dscale is None and dshift is None:
+      return (None,) * 6
+    address = lambda tensor: None if tensor is None else tensor.data_ptr()
+    api.emb_norm_act_grad(
+        flat.data_ptr(), address(scale), address(shift), gout.data_ptr(), _DTYPES[flat.dtype], rows, units, impl, act,
+        eps, address(dx), address(dscale), address(dshift), address(partials), floats, _lib.raw_stream(flat.device))
+    if ctx.needs_input_grad[2] and dshift is None:      # rms does not read its shift
+      dshift = torch.zeros_like(shift)
+    return (None if dx is None else dx.view(shape), dscale, dshift, None, None, None)
+
+
+def _eps_of(impl, eps):
+  """nets.py:369-371: 'rms1em6' is rms with eps = 10 ** -6."""
+  if isinstance(impl, str) and '1em' in impl:
+    impl, exp = impl.split('1em')
+    eps = 10 ** -int(exp)
+  return impl, eps
+
+
+def norm_act(x, scale=None, shift=None, impl='rms', act='silu', eps=1e-4, fused=None):
+  """`nn.act(act)(Norm(impl)(x))` (nets.py:361-399, nets.py:26-39) over the last
+  axis of a CUDA tensor of float32 or bfloat16 with any leading shape; the result
+  has the shape and dtype of `x` and is differentiable once with respect to `x`,
+  `scale` and `shift`.
+
+    rms    y = x * (rsqrt(mean(x^2) + eps) * scale)
+    layer  y = (x - mean) * (rsqrt(max(0, mean(x^2) - mean^2) + eps) * scale) + shift
+
+  `scale` and `shift` are float32 `(units,)` or None (ones / zeros); `rms` takes
+  no shift.  `impl` may carry the reference's eps suffix ('rms1em6').  `act` is
+  'none', 'silu', 'gelu' (the tanh approximation, jax.nn.gelu's default) or 'relu'.
+
+  Two paths.  Composed restates the reference operation by operation in torch
+  (the definition, every size): float32 inside the norm, rounded to the dtype of
+  `x`, the activation in that dtype.  Fused is `emb_norm_act` /
+  `emb_norm_act_grad`: 1 .. 16 384 units, one launch forward; backward one
+  launch, two with a gradient for `scale` or `shift`; no atomics, the same bits
+  run to run.  `fused=None` takes the kernels where they fit, True / False force
+  a path (True raises where they do not fit, and says why).  No rows: the composed
+  path, nothing is launched.
+
+  The documented difference: the kernels apply the activation to the float32
+  value and round once; the reference rounds to the compute dtype between norm
+  and activation (nets.py:398).  For float32 inputs there is none.
+
+  Non-finite inputs.  On the kernels a row with a NaN or an infinite element (or
+  whose squares overflow float32) is NaN throughout, in the output and in `dx`,
+  and no other row is touched; the gradients of `scale` and `shift` sum over it.
+  Composed is the definition: an infinite element makes its row's rstd 0, so the
+  row's finite elements come out 0 and the infinite one NaN."""
+  _check_device('norm_act', x)
+  if x.dtype not in _DTYPES:
+    raise TypeError(f'norm_act: x must be float32 or bfloat16, got {x.dtype}')
+  impl, eps = _eps_of(impl, eps)
+  if impl not in IMPLS:
+    raise ValueError(f'norm_act: impl = {impl!r}, needs one of {sorted(IMPLS)}')
+  if act not in ACTS:
+    raise ValueError(f'norm_act: act = {act!r}, needs one of {sorted(ACTS)}')
+  eps = float(eps)
+  if not (np.isfinite(eps) and eps >= 0):
+    raise ValueError(f'norm_act: eps = {eps}, needs a finite value that is not negative')
+  if x.dim() < 1 or x.shape[-1] < 1:
+    raise ValueError(f'norm_act: x of shape {tuple(x.shape)}, needs (..., units)')
+  units = x.shape[-1]
+  scale = _check_param('norm_act', 'scale', scale, units, x)
+  shift = _check_param('norm_act', 'shift', shift, units, x)
+  if impl == 'rms' and shift is not None:
+    raise ValueError('norm_act: rms takes no shift (nets.py:382-386)')
+  rows = int(np.prod(x.shape[:-1], dtype=np.int64))
+  if _norm_path(fused, rows, units) and rows > 0:
+    return _FusedNormAct.apply(x, scale, shift, IMPLS[impl], ACTS[act], eps)
+  return _composed_norm_act(x, scale, shift, impl, act, eps)
+
+
+class NormAct(torch.nn.Module):
+  """`nn.act(act)(Norm(impl)(x))` with the norm's parameters: float32 `scale`
+  (ones, nets.py:401-404) and, for 'layer', `shift` (zeros, nets.py:406-409);
+  `scale=False` / `shift=False` leave one out, as the reference's fields do.
+  `impl` takes the reference's 'rms1em6' spelling of eps (nets.py:369-371).
+  Parameters are made on `device` (default: the current CUDA device)."""
+
+  def __init__(self, units, impl='rms', act='silu', eps=1e-4, scale=True, shift=True, fused=None, device=None):
+    super().__init__()
+    impl, eps = _eps_of(impl, eps)
+    if impl not in IMPLS:
+      raise ValueError(f'NormAct: impl = {impl!r}, needs one of {sorted(IMPLS)}')
+    if act not in ACTS:
+      raise ValueError(f'NormAct: act = {act!r}, needs one of {sorted(ACTS)}')
+    if int(units) < 1:
+      raise ValueError(f'NormAct: units = {units}, needs at least 1')
+    self.units, self.impl, self.act, self.eps, self.fused = int(units), impl, act, float(eps), fused
+    device = 'cuda' if device is None else device
+    self.scale = torch.nn.Parameter(torch.ones(self.units, dtype=torch.float32, device=device)) if scale else None
+    self.shift = (torch.nn.Parameter(torch.zeros(self.units, dtype=torch.float32, device=device))
+                  if shift and impl == 'layer' else None)
+
+  def forward(self, x):
+    return norm_act(x, self.scale, self.shift, self.impl, self.act, self.eps, self.fused)
+
+  def extra_repr(self):
+    return f'{self.units}, impl={self.impl!r}, act={self.act!r}, eps={self.eps:g}'
+
+
+def _composed_gru_gate(x, deter, blocks):
+  """rssm.py:139-140, 153-158 operation by operation, in the dtype of `x`."""
+  lead, width = deter.shape[:-1], deter.shape[-1]
+  grouped = x.reshape(*lead, blocks, 3 * width // blocks)                       # flat2group
+  gates = torch.split(grouped, width // blocks, -1)
+  reset, cand, update = [g.reshape(*lead, width) for g in gates]               # group2flat
+  reset = torch.sigmoid(reset)
+  cand = torch.tanh(reset * cand)
+  update = torch.sigmoid(update - 1)
+  return update * cand + (1 - update) * deter
+
+
+class _FusedGate(torch.autograd.Function):
+  """The new deter on the kernels: one launch forward, one backward."""
+
+  @staticmethod
+  def forward(ctx, x, deter, blocks):
+    width = deter.shape[-1]
+    xs = x.detach().reshape(-1, 3 * width).contiguous()
+    ds = deter.detach().reshape(-1, width).contiguous()
+    out = torch.empty_like(ds)
+    api.emb_gru_gate(xs.data_ptr(), ds.data_ptr(), _DTYPES[xs.dtype], ds.shape[0], width, blocks, out.data_ptr(),
+                     _lib.raw_stream(xs.device))
+    ctx.saved = (xs, ds, blocks, x.shape, deter.shape)
+    ctx.set_materialize_grads(False)
+    return out.view(deter.shape)
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    if gout is None:
+      return None, None, None
+    xs, ds, blocks, xshape, dshape = ctx.saved
+    want_x, want_deter = ctx.needs_input_grad[:2]
+    if not (want_x or want_deter):
+      return None, None, None
+    gout = gout.to(ds.dtype).reshape(ds.shape).contiguous()
+    dx = torch.empty_like(xs) if want_x else None
+    ddeter = torch.empty_like(ds) if want_deter else None
+    address = lambda tensor: None if tensor is None else tensor.data_ptr()
+    api.emb_gru_gate_grad(xs.data_ptr(), ds.data_ptr(), gout.data_ptr(), _DTYPES[ds.dtype], ds.shape[0], ds.shape[1],
+                          blocks, address(dx), address(ddeter), _lib.raw_stream(ds.device))
+    return (None if dx is None else dx.view(xshape), None if ddeter is None else ddeter.view(dshape), None)
+
+
+def gru_gate(x, deter, blocks, fused=None):
+  """The tail of `RSSM._core` (rssm.py:152-159): the new `deter`, in the shape and
+  dtype of `deter`, from `x` (..., 3 * deter), the output of the `dyngru`
+  BlockLinear, and the old `deter` (..., deter); `blocks` divides deter and
+  h = deter / blocks.  For block k and j < h
+
+      reset  = sigmoid(x[..., 3hk + j])
+      cand   = tanh(reset * x[..., 3hk + h + j])
+      update = sigmoid(x[..., 3hk + 2h + j] - 1)
+      out[..., hk + j] = update * cand + (1 - update) * deter[..., hk + j]
+
+  differentiable once with respect to `x` and `deter`.  Both are CUDA tensors of
+  one dtype, float32 or bfloat16.
+
+  Two paths, as `norm_act`.  Composed is the reference's reshape, split and
+  elementwise operations in the dtype of `x`; fused is `emb_gru_gate` /
+  `emb_gru_gate_grad`, float32 arithmetic rounded once at the store, ONE launch
+  forward and ONE backward, the split done by index arithmetic.  Saturated gates
+  give finite values and zero or tiny gradients; a NaN touches the output
+  element and the gradient elements it feeds, nothing else.  No rows: the
+  composed path, nothing is launched."""
+  _check_device('gru_gate', x)
+  _check_device('gru_gate', deter)
+  if x.dtype not in _DTYPES:
+    raise TypeError(f'gru_gate: x must be float32 or bfloat16, got {x.dtype}')
+  if deter.dtype != x.dtype:
+    raise TypeError(f'gru_gate: deter is {deter.dtype}, x is {x.dtype}: one dtype for both')
+  if deter.device != x.device:
+    raise ValueError(f'gru_gate: deter on {deter.device}, x on {x.device}')
+  if deter.dim() < 1 or deter.shape[-1] < 1:
+    raise ValueError(f'gru_gate: deter of shape {tuple(deter.shape)}, needs (..., deter)')
+  width = deter.shape[-1]
+  if tuple(x.shape) != (*deter.shape[:-1], 3 * width):
+    raise ValueError(f'gru_gate: x of shape {tuple(x.shape)}, deter {tuple(deter.shape)} needs '
+                     f'{(*deter.shape[:-1], 3 * width)}')
+  blocks = int(blocks)
+  if blocks < 1 or width % blocks:
+    raise ValueError(f'gru_gate: blocks = {blocks} does not divide deter = {width} (rssm.py:35)')
+  rows = int(np.prod(deter.shape[:-1], dtype=np.int64))
+  if _gate_path(fused, rows, width, blocks) and rows > 0:
+    return _FusedGate.apply(x, deter, blocks)
+  return _composed_gru_gate(x, deter, blocks)

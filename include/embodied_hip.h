@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports (133 functions). */
+ * it exports (139 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -46,7 +46,9 @@ extern "C" {
  * emb_twohot_grad, emb_twohot_launches, emb_onehot_kl, emb_onehot_kl_grad,
  * emb_onehot_kl_launches, emb_policy_loss, emb_policy_loss_grad,
  * emb_policy_loss_launches, emb_optim_table, emb_optim_norms, emb_optim_update,
- * emb_optim_metrics, emb_optim_launches (additions only).                     */
+ * emb_optim_metrics, emb_optim_launches, emb_norm_act, emb_norm_act_grad,
+ * emb_norm_act_launches, emb_gru_gate, emb_gru_gate_grad, emb_gru_gate_launches
+ * (additions only).                                                            */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -828,6 +830,81 @@ int32_t emb_optim_metrics(const void* partials, int64_t n_chunks, int64_t count,
 /* Kernel launches the three entry points above have issued in this process,
  * counted where the kernels are launched.                                      */
 int32_t emb_optim_launches(int64_t* count);
+
+/* ---- Norm followed by the activation, float32 arithmetic on device
+ * embodied/jax/nets.py:361-399 (Norm.__call__) and then embodied/jax/nets.py:26-39
+ * (act): what follows every Linear, BlockLinear and Conv2D of DreamerV3's
+ * networks -- inside RSSM._core four times (dreamerv3/rssm.py:141-151), once in
+ * _observe (dreamerv3/rssm.py:83-85) and twice in _prior (dreamerv3/rssm.py:163-165).
+ * `x` and `out` are (rows, units) contiguous on device, dtype EMB_F32 or EMB_BF16
+ * (widened in registers); `scale` and `shift` are (units,) float32 on device, or
+ * NULL: ones / zeros.  Per row, every operation in float32 and on its own:
+ *   EMB_NORM_RMS    y = x * (rsqrt(mean(x^2) + eps) * scale)          (nets.py:383-386)
+ *   EMB_NORM_LAYER  y = (x - mean) * (rsqrt(max(0, mean(x^2) - mean^2) + eps) * scale)
+ *                       + shift          (nets.py:388-395: the one-pass variance)
+ *   out = act(y): EMB_ACT_NONE, EMB_ACT_SILU y sigmoid(y), EMB_ACT_GELU the tanh
+ *         approximation (jax.nn.gelu's default), EMB_ACT_RELU max(y, 0)
+ * The activation works on the float32 y and the result is rounded once at the
+ * store; the reference rounds y to the compute dtype first (nets.py:398).
+ * EMB_NORM_RMS ignores `shift`.
+ *   emb_norm_act       one launch; x is read once.
+ *   emb_norm_act_grad  dx (rows, units) in the dtype of x -- gout's too -- and
+ *                      dscale, dshift (units,) float32, each NULL or written, all
+ *                      recomputed from x.  With dscale or dshift every workgroup
+ *                      leaves its rows' column sums in `partials` (float32 on
+ *                      device, `partial_floats` of them: at least 2 * P * units
+ *                      with P = min(ceil(rows / (units <= 1024 ? 4 : 1)), 512)) and
+ *                      a second launch adds them in a fixed order; without, one
+ *                      launch and `partials` is not used.
+ * No atomics: the same bits run to run.  A row whose mean(x^2) is NaN or
+ * infinite is NaN throughout in out and dx, and touches no other row; dscale and
+ * dshift sum over it.
+ * EMB_ERR_INVALID before any launch: an unknown dtype, impl or act, rows < 0,
+ * units outside 1 .. 16384, more than 2^31 - 1 elements, a negative or non-finite
+ * eps, and with rows > 0 a NULL x, out or gout, no output at all, or partials
+ * that are NULL or too small.  rows = 0: EMB_OK, nothing is launched or written. */
+#define EMB_NORM_RMS 0
+#define EMB_NORM_LAYER 1
+#define EMB_ACT_NONE 0
+#define EMB_ACT_SILU 1
+#define EMB_ACT_GELU 2
+#define EMB_ACT_RELU 3
+int32_t emb_norm_act(const void* x, const void* scale, const void* shift, int32_t dtype, int64_t rows, int64_t units,
+                     int32_t impl, int32_t act, float eps, void* out, void* stream);
+int32_t emb_norm_act_grad(const void* x, const void* scale, const void* shift, const void* gout, int32_t dtype,
+                          int64_t rows, int64_t units, int32_t impl, int32_t act, float eps, void* dx, void* dscale,
+                          void* dshift, void* partials, int64_t partial_floats, void* stream);
+/* Kernel launches the two entry points above have issued in this process,
+ * counted where the kernels are launched.                                      */
+int32_t emb_norm_act_launches(int64_t* count);
+
+/* ---- the blocked GRU gate of the RSSM, float32 arithmetic on device
+ * The tail of RSSM._core, dreamerv3/rssm.py:152-159: `x` (rows, 3 * deter) is what
+ * the `dyngru` BlockLinear leaves, `deter` and `out` are (rows, deter), all
+ * contiguous on device in one dtype, EMB_F32 or EMB_BF16.  `blocks` divides
+ * deter, h = deter / blocks; for block k and j < h (rssm.py:153-154)
+ *   reset  = sigmoid(x[r, 3hk + j])                                (rssm.py:155)
+ *   cand   = tanh(reset * x[r, 3hk + h + j])                       (rssm.py:156)
+ *   update = sigmoid(x[r, 3hk + 2h + j] - 1)                       (rssm.py:157)
+ *   out[r, hk + j] = update * cand + (1 - update) * deter[r, hk + j]   (rssm.py:158)
+ * rounded once at the store.  The split is index arithmetic: nothing is copied.
+ *   emb_gru_gate       one launch.
+ *   emb_gru_gate_grad  one launch: dx (rows, 3 * deter) and ddeter (rows, deter)
+ *                      from x, deter and gout (rows, deter), in their dtype;
+ *                      either may be NULL (not written).
+ * Elementwise: a saturated gate gives finite values and a zero or tiny gradient, a
+ * NaN touches the output element and the gradient elements it feeds.
+ * EMB_ERR_INVALID before any launch: an unknown dtype, rows < 0, deter < 1, a
+ * `blocks` below 1 or that does not divide deter, more than 2^31 - 1 elements of
+ * x, and with rows > 0 a NULL input or no output.  rows = 0: EMB_OK, nothing is
+ * launched.                                                                    */
+int32_t emb_gru_gate(const void* x, const void* deter, int32_t dtype, int64_t rows, int64_t width, int64_t blocks,
+                     void* out, void* stream);
+int32_t emb_gru_gate_grad(const void* x, const void* deter, const void* gout, int32_t dtype, int64_t rows,
+                          int64_t width, int64_t blocks, void* dx, void* ddeter, void* stream);
+/* Kernel launches the two entry points above have issued in this process,
+ * counted where the kernels are launched.                                      */
+int32_t emb_gru_gate_launches(int64_t* count);
 
 /* ----------------------------------------------------------- collectives --
  * The two exchange steps of the sharded path on RCCL directly (xGMI inside one
