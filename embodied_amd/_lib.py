@@ -223,6 +223,10 @@ SIGNATURES = {
     'emb_gru_gate': [p, p, i32, i64, i64, i64, p, p],
     'emb_gru_gate_grad': [p, p, p, i32, i64, i64, i64, p, p, p],
     'emb_gru_gate_launches': [p],
+    'emb_philox_uniform': [u64, u64, u64, i64, p, p],
+    'emb_onehot_sample': [p, i32, i64, i64, i64, f32, i32, u64, u64, p, p, p, p],
+    'emb_onehot_sample_grad': [p, p, i32, i64, i64, i64, f32, p, p],
+    'emb_onehot_sample_launches': [p],
     'emb_synth_env_step': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p],
     'emb_synth_env_step_masked': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p, p, i64, i32, p],
     'emb_env_mask_supported': [i64, i32],

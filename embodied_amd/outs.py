@@ -1,9 +1,11 @@
 """Output heads on device: the `symexp_twohot` head of DreamerV3's reward and
 value networks (embodied/jax/heads.py:132-144, embodied/jax/outs.py:273-330),
 the one-hot latents' KL pair of its world model (`OneHot`, `rssm_kl`:
-dreamerv3/rssm.py:123-132, embodied/jax/outs.py:40-76, 208-263), and the
+dreamerv3/rssm.py:123-132, embodied/jax/outs.py:40-76, 208-263), the
 actor's discrete policy head and loss (`Categorical`, `policy_loss`:
-dreamerv3/agent.py:411-415, embodied/jax/outs.py:208-240).
+dreamerv3/agent.py:411-415, embodied/jax/outs.py:208-240), and the draw of
+both (`OneHot.sample` / `pred`, `Categorical.sample`: dreamerv3/rssm.py:87, 100,
+dreamerv3/agent.py:18, 126, 192, embodied/jax/outs.py:219-224, 248-254, 265-270).
 
 It sits on both sides of `scans.dreamer_targets`: that function's `pred`
 argument is `value.pred()` / `slowvalue.pred()` and its `tar_padded` result goes
@@ -466,16 +468,193 @@ def _rows_of(logits):
   return int(np.prod(logits.shape[:-2], dtype=np.int64))
 
 
+# ---- the draw: OneHot.sample / pred, Categorical.sample ----------------------
+
+# What the kernels take: a group of at most 256 classes stays in one wave's
+# registers, indices are 32-bit.  Structural, not a crossover: the fused median
+# is below the composed one at all 28 rows of profiles/onehot_sample_bench.txt
+# (rows 16, 1024 and 16 384 of (32, 32), (32, 64), (32, 65) and the actor's (1, 18),
+# float32 and bfloat16, forward and forward + backward), and below the
+# torch.multinomial composition's at every one too, so no size constant sits
+# beside `_sample_path`; the figures are quoted there.
+SAMPLE_MAX_CLASSES = 256
+SAMPLE_MAX_LOGITS = 2 ** 31 - 1
+_SAMPLE_DRAW, _SAMPLE_PRED = 0, 1
+
+
+def onehot_sample_launches():
+  """Kernel launches `emb_philox_uniform`, `emb_onehot_sample` and
+  `emb_onehot_sample_grad` have issued in this process."""
+  count = C.c_int64(0)
+  api.emb_onehot_sample_launches(C.byref(count))
+  return count.value
+
+
+def _check_counter(who, name, value):
+  if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+    raise TypeError(f'{who}: {name} must be an integer, got {type(value).__name__}')
+  value = int(value)
+  if not 0 <= value < 2 ** 64:
+    raise ValueError(f'{who}: {name} = {value}, needs 0 <= {name} < 2^64')
+  return value
+
+
+def philox_uniform(seed, offset=0, first=0, count=1, device=None):
+  """(count,) float32 on `device`: the uniforms the sample kernels draw for the
+  groups `first .. first + count - 1` -- Philox4x32-10 with key
+  (seed & 0xffffffff, seed >> 32) and counter (g & 0xffffffff, g >> 32,
+  offset & 0xffffffff, offset >> 32), u = (word 0 >> 8) * 2^-24 in [0, 1).  One
+  launch (`emb_philox_uniform`); count = 0 launches nothing."""
+  seed = _check_counter('philox_uniform', 'seed', seed)
+  offset = _check_counter('philox_uniform', 'offset', offset)
+  first = _check_counter('philox_uniform', 'first', first)
+  count = int(count)
+  if count < 0 or first + count > 2 ** 64:
+    raise ValueError(f'philox_uniform: count = {count} from first = {first}, needs 0 <= count and groups below 2^64')
+  device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+  if device.type != 'cuda':
+    raise RuntimeError('embodied_amd.outs runs as HIP kernels: pass a CUDA device (no CPU fallback)')
+  out = torch.empty((count,), dtype=torch.float32, device=device)
+  if count:
+    api.emb_philox_uniform(seed, offset, first, count, out.data_ptr(), _lib.raw_stream(out.device))
+  return out
+
+
+def _sample_path(who, fused, rows, groups, classes):
+  """True: the kernels, False: the composed path (`OneHot.sample` says when).
+  The kernels' median was below the composed path's at every shape, dtype and
+  piece measured (profiles/onehot_sample_bench.txt) -- the RSSM's observe step,
+  (16, 32, 32) f32: forward 17.9 us against 274.4, forward + backward 113.7
+  against 416.5; its imagination step, (1024, 32, 32) f32: 17.0 / 244.0 and 70.4 /
+  328.4; (16384, 32, 64) bf16: 238.5 / 3619.9 and 465.0 / 4162.9 -- so `fused=None`
+  takes them wherever they fit.  Up to 1024 rows the fused forward is the host's
+  enqueue, about 17 us whatever the size (the entry point alone: 4 .. 18 us)."""
+  fits = 1 <= classes <= SAMPLE_MAX_CLASSES and groups >= 1 and rows * groups * classes <= SAMPLE_MAX_LOGITS
+  if fused and not 1 <= classes <= SAMPLE_MAX_CLASSES:
+    raise ValueError(
+        f'{who}(fused=True): {classes} classes, the kernels keep a group of at most {SAMPLE_MAX_CLASSES} in one '
+        'wave\'s registers (fused=None or False composes it)')
+  if fused and not fits:
+    raise ValueError(
+        f'{who}(fused=True): {rows} x {groups} x {classes} logits, the kernels index 1 .. 2^31 - 1 '
+        '(fused=None or False composes it)')
+  if fused is None:
+    return fits
+  return bool(fused)
+
+
+def _sample_args(who, logits, seed, offset, uniform):
+  """(seed, offset, uniform) checked; `uniform` None or float32 on the logits'
+  device, one value per group, contiguous."""
+  if not logits.is_contiguous():
+    raise ValueError(f'{who}: logits of shape {tuple(logits.shape)} and strides {logits.stride()} are not contiguous')
+  offset = _check_counter(who, 'offset', offset)
+  if uniform is None:
+    return _check_counter(who, 'seed', seed), offset, None
+  seed = 0 if seed is None else _check_counter(who, 'seed', seed)
+  if not (torch.is_tensor(uniform) and uniform.dtype == torch.float32 and uniform.device == logits.device):
+    raise TypeError(f'{who}: uniform must be a float32 tensor on {logits.device}')
+  if uniform.shape != logits.shape[:-1] or not uniform.is_contiguous():
+    raise ValueError(f'{who}: uniform of shape {tuple(uniform.shape)}, needs a contiguous {tuple(logits.shape[:-1])}')
+  return seed, offset, uniform.detach()
+
+
+def _fused_sample(x, rows, groups, unimix, mode, seed, offset, uniform, want_index, want_onehot):
+  """One launch: (index int32 (rows * groups,) or None, onehot like x or None)."""
+  index = _lib.empty((rows * groups,), torch.int32, x.device) if want_index else None
+  onehot = torch.empty_like(x) if want_onehot else None
+  address = lambda t: None if t is None else t.data_ptr()
+  api.emb_onehot_sample(
+      x.data_ptr(), _DTYPES[x.dtype], rows, groups, x.shape[-1], unimix, mode, seed, offset, address(uniform),
+      address(index), address(onehot), _lib.raw_stream(x.device))
+  return index, onehot
+
+
+class _FusedSample(torch.autograd.Function):
+  """The straight-through one-hot on the kernels: one launch forward, one backward."""
+
+  @staticmethod
+  def forward(ctx, logits, geometry, unimix, mode, seed, offset, uniform):
+    rows, groups = geometry
+    x = logits.detach()
+    onehot = _fused_sample(x, rows, groups, unimix, mode, seed, offset, uniform, False, True)[1]
+    ctx.saved = (x, rows, groups, unimix)
+    ctx.set_materialize_grads(False)
+    return onehot
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    if gout is None:
+      return (None,) * 7
+    x, rows, groups, unimix = ctx.saved
+    gout = gout.to(x.dtype).contiguous()
+    grad = torch.empty_like(x)
+    api.emb_onehot_sample_grad(
+        x.data_ptr(), gout.data_ptr(), _DTYPES[x.dtype], rows, groups, x.shape[-1], unimix, grad.data_ptr(),
+        _lib.raw_stream(x.device))
+    return (grad,) + (None,) * 6
+
+
+def _composed_uniform(logits, seed, offset, uniform):
+  """One uniform per group, shaped as the logits without their classes: the
+  caller's, or the Philox stream the kernels draw from."""
+  if uniform is not None:
+    return uniform
+  shape = logits.shape[:-1]
+  return philox_uniform(seed, offset, 0, int(np.prod(shape, dtype=np.int64)), logits.device).view(shape)
+
+
+def _composed_index(probs, u):
+  """The smallest k with p_k > 0 and C_k > u C_last, C = cumsum(p) in float32; none
+  (rounding): the last class with p > 0; a group whose probabilities are NaN: -1."""
+  cdf = torch.cumsum(probs, -1)
+  hit = (cdf > u[..., None] * cdf[..., -1:]) & (probs > 0)
+  index = torch.argmax(hit.to(torch.int8), -1)                       # the first True
+  classes = probs.shape[-1]
+  last = classes - 1 - torch.argmax((probs > 0).flip(-1).to(torch.int8), -1)
+  index = torch.where(hit.any(-1), index, last)
+  return torch.where(torch.isnan(probs).any(-1), -1, index)
+
+
+def _composed_value(logits, unimix, index):
+  """outs.py:265-270, `_onehot_with_grad`, in float32 and cast to the logits' dtype.
+  `index` -1 (a group of NaN probabilities): the row is NaN by `probs - sg(probs)`."""
+  dist = _onehot_logits(logits, unimix)
+  value = torch.nn.functional.one_hot(index.clamp(min=0).to(torch.int64), logits.shape[-1]).to(torch.float32)
+  probs = torch.softmax(dist, -1)
+  value = value.detach() + (probs - probs.detach())
+  return value.to(logits.dtype)
+
+
+def _composed_draw(logits, unimix, seed, offset, uniform):
+  """int64 indices, shaped as the logits without their classes, no gradient."""
+  with torch.no_grad():
+    probs = torch.softmax(_onehot_logits(logits, unimix), -1)        # outs.py:210-217, then what :223 samples from
+    return _composed_index(probs, _composed_uniform(logits, seed, offset, uniform))
+
+
+def _composed_argmax(logits):
+  """argmax(x), the first on ties; a group with a NaN or +inf logit or nothing but -inf: -1."""
+  with torch.no_grad():
+    x = logits.to(torch.float32)
+    top = x.amax(-1)
+    bad = torch.isnan(x).any(-1) | torch.isinf(top)
+    return torch.where(bad, -1, torch.argmax(x, -1))
+
+
 class OneHot:
   """The reference's `Agg(OneHot(logits, unimix), 1, sum)` (rssm.py:173-176,
   outs.py:40-76, 208-263) over `logits` (..., stoch, classes), a CUDA tensor of
-  float32 or bfloat16: `.entropy()` and `.kl(other)`, each (...) float32.  The
-  reference computes in float32 (outs.py:211) and so does this; bfloat16 logits
-  are widened in registers and the gradients come back in bfloat16.
+  float32 or bfloat16: `.entropy()` and `.kl(other)`, each (...) float32, and
+  `.sample(seed)` / `.pred()`, the straight-through one-hot shaped and typed like
+  the logits.  The reference computes in float32 (outs.py:211) and so does this;
+  bfloat16 logits are widened in registers and the gradients come back in bfloat16.
 
   Two paths, as `TwoHot`: composed restates the reference line by line in torch
-  (the definition, every size); fused is `emb_onehot_kl` / `emb_onehot_kl_grad`,
-  classes <= 256.  `fused=None` takes the kernels where they fit, True / False
+  (the definition, every size); fused is `emb_onehot_kl` / `emb_onehot_kl_grad`
+  and `emb_onehot_sample` / `emb_onehot_sample_grad`, classes <= 256.
+  `fused=None` takes the kernels where they fit, True / False
   force a path (True raises where they do not fit, and says why).  No rows: the
   composed path, nothing is launched.  `rssm_kl` documents the arithmetic and
   the non-finite logits."""
@@ -488,6 +667,54 @@ class OneHot:
     rows = _rows_of(logits)
     self._fused_arg = fused
     self.fused = _kl_path(fused, rows, *logits.shape[-2:]) and rows > 0
+
+  def _sample_fused(self):
+    rows, (groups, classes) = _rows_of(self.logits), self.logits.shape[-2:]
+    return _sample_path('OneHot', self._fused_arg, rows, groups, classes) and rows * groups > 0
+
+  def sample(self, seed=None, offset=0, uniform=None):
+    """rssm.py:87, 100 over outs.py:252-254, 265-270: one class per group drawn
+    from p = (1 - unimix) softmax(logits) + unimix / classes, as the straight-through
+    one-hot `sg(onehot) + (probs - sg(probs))` -- exactly 0 or 1, shaped and typed
+    like the logits, differentiable once: the gradient is
+    (1 - unimix) s (g - sum_k s_k g_k), s = softmax(logits), whatever was drawn.
+
+    The draw is the inverse CDF of one uniform per group: the smallest k with
+    p_k > 0 and C_k > u C_last, C the float32 prefix sum of p in class order (a
+    class of probability exactly 0 is never returned).  u comes from
+    Philox4x32-10 keyed by `seed` at counter (g, `offset`), g the group's flat
+    index (`philox_uniform`): it depends on (seed, offset, g) alone, not on the
+    dtype, the path, the launch geometry or the rows that follow.  Give every
+    call its own `offset` (a step counter) or `seed`; both are integers in
+    [0, 2^64).  `uniform`, a float32 tensor of one value in [0, 1) per group
+    (shaped as the logits without their classes), replaces the counter for
+    callers who bring their own generator.  It is also the way to fresh draws
+    inside a captured graph: `seed` and `offset` travel to the kernel by value,
+    so a replayed graph repeats the draw it captured, while a `uniform` tensor
+    refilled between replays is read anew.
+
+    On the kernels that is ONE launch forward and ONE backward; the composed
+    path draws the same uniforms with `emb_philox_uniform` and takes `cumsum`,
+    the comparison and `argmax`, so both paths draw the same class except
+    where u lies within rounding of a boundary of the CDF.  The logits must be
+    contiguous.  A group with a NaN or +inf logit, or nothing but -inf, gives a
+    NaN row and a NaN gradient, and touches no other group."""
+    seed, offset, uniform = _sample_args('OneHot.sample', self.logits, seed, offset, uniform)
+    if self._sample_fused():
+      geometry = (_rows_of(self.logits), self.logits.shape[-2])
+      return _FusedSample.apply(self.logits, geometry, self.unimix, _SAMPLE_DRAW, seed, offset, uniform)
+    index = _composed_draw(self.logits, self.unimix, seed, offset, uniform)
+    return _composed_value(self.logits, self.unimix, index)
+
+  def pred(self):
+    """outs.py:248-250: the straight-through one-hot of argmax(logits), the first
+    class on ties (the mix is increasing in the logits, so it is the argmax of
+    outs.py:219-220 too); same gradient, launches and non-finite groups as `sample`."""
+    _sample_args('OneHot.pred', self.logits, 0, 0, None)
+    if self._sample_fused():
+      geometry = (_rows_of(self.logits), self.logits.shape[-2])
+      return _FusedSample.apply(self.logits, geometry, self.unimix, _SAMPLE_PRED, 0, 0, None)
+    return _composed_value(self.logits, self.unimix, _composed_argmax(self.logits))
 
   def entropy(self):
     """(...) float32, no gradient: the reference uses it for metrics only
@@ -711,8 +938,8 @@ class Categorical:
   `.logp(act)` and `.entropy()` are (...) float32 and differentiable once with
   respect to the logits (the entropy is part of the actor's loss, agent.py:412-414);
   `.pred()` is the argmax (composed torch ops).  `.minent = 0` and
-  `.maxent = log(classes) * groups` are what agent.py:440-442 reads.  `sample` is
-  not provided.  An action outside [0, classes) has log-probability 0, as the row
+  `.maxent = log(classes) * groups` are what agent.py:440-442 reads.  `.sample(seed)`
+  draws int32 actions (`emb_onehot_sample`).  An action outside [0, classes) has log-probability 0, as the row
   of zeros `jax.nn.one_hot` gives it; it is never used as an address.
 
   Two paths, as `OneHot`: composed restates the reference line by line in torch
@@ -732,6 +959,7 @@ class Categorical:
     self._groups = logits.shape[-2] if dims else 1
     self._classes = logits.shape[-1]
     self._rows = int(np.prod(self._lead, dtype=np.int64))
+    self._fused_arg = fused
     self.fused = _policy_path(fused, self._rows, self._groups, self._classes) and self._rows > 0 and self._groups > 0
     self.minent = 0.0
     self.maxent = float(np.log(self._classes)) * self._groups
@@ -743,6 +971,23 @@ class Categorical:
   def pred(self):
     """outs.py:219-220: the argmax over the classes, int64, (...) or (..., groups)."""
     return torch.argmax(_onehot_logits(self.logits.detach(), self.unimix), -1)
+
+  def sample(self, seed=None, offset=0, uniform=None):
+    """agent.py:18, 126, 192 over outs.py:222-224: int32 class indices shaped as the
+    logits without their classes, (...) or (..., groups), no gradient -- what
+    `logp` and `policy_loss` take as `act`.  The draw, `seed`, `offset` and
+    `uniform` are `OneHot.sample`'s: the same kernel with the one-hot store off,
+    so both return the same class for the same (seed, offset).  `seed` and
+    `offset` travel by value and replay as captured inside a graph; `uniform`
+    is read anew.  The logits must be contiguous.  A group with a NaN or +inf
+    logit, or nothing but -inf: -1."""
+    seed, offset, uniform = _sample_args('Categorical.sample', self.logits, seed, offset, uniform)
+    count = self._rows * self._groups
+    if _sample_path('Categorical', self._fused_arg, self._rows, self._groups, self._classes) and count > 0:
+      index = _fused_sample(self.logits.detach(), self._rows, self._groups, self.unimix, _SAMPLE_DRAW, seed, offset,
+                            uniform, True, False)[0]
+      return index.view(self.logits.shape[:-1])
+    return _composed_draw(self.logits.detach(), self.unimix, seed, offset, uniform).to(torch.int32)
 
   def logp(self, act):
     """(...) float32: the log-probability of `act` (int32 or int64; a constant)."""

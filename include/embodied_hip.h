@@ -47,8 +47,9 @@ extern "C" {
  * emb_onehot_kl_launches, emb_policy_loss, emb_policy_loss_grad,
  * emb_policy_loss_launches, emb_optim_table, emb_optim_norms, emb_optim_update,
  * emb_optim_metrics, emb_optim_launches, emb_norm_act, emb_norm_act_grad,
- * emb_norm_act_launches, emb_gru_gate, emb_gru_gate_grad, emb_gru_gate_launches
- * (additions only).                                                            */
+ * emb_norm_act_launches, emb_gru_gate, emb_gru_gate_grad, emb_gru_gate_launches,
+ * emb_philox_uniform, emb_onehot_sample, emb_onehot_sample_grad,
+ * emb_onehot_sample_launches (additions only).                                 */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -905,6 +906,54 @@ int32_t emb_gru_gate_grad(const void* x, const void* deter, const void* gout, in
 /* Kernel launches the two entry points above have issued in this process,
  * counted where the kernels are launched.                                      */
 int32_t emb_gru_gate_launches(int64_t* count);
+
+/* ---- the draw of a one-hot latent or a discrete action, float32 arithmetic on device
+ * DreamerV3 samples its stochastic state once per step of RSSM._observe and
+ * RSSM.imagine, `self._dist(logit).sample(seed)` (dreamerv3/rssm.py:87, 100), and
+ * the actor's action the same way (dreamerv3/agent.py:18, 126, 192), over OneHot /
+ * Categorical (embodied/jax/outs.py:208-224 Categorical.__init__, pred, sample;
+ * 243-254 OneHot.pred, sample; 265-270 _onehot_with_grad).  `logits` is
+ * (rows, groups, classes), contiguous on device, EMB_F32 or EMB_BF16; group
+ * g = row * groups + group.  Per group
+ *   p = (1 - unimix) softmax(x) + unimix / classes                  (outs.py:212-216)
+ *   u = uniform[g] (float32, in [0, 1)) or, with uniform NULL, Philox4x32-10 with
+ *       key (seed & 0xffffffff, seed >> 32) and counter (g & 0xffffffff, g >> 32,
+ *       offset & 0xffffffff, offset >> 32): u = (word 0 >> 8) * 2^-24.  The draw
+ *       depends on (seed, offset, g) and on nothing else.
+ *   EMB_SAMPLE_DRAW  index = the smallest k with p_k > 0 and C_k > u * C_last, C the
+ *                    inclusive float32 prefix sum of p in class order; if rounding
+ *                    leaves none, the last class with p > 0      (outs.py:222-224)
+ *   EMB_SAMPLE_PRED  index = argmax(x), the first on ties; no uniform (outs.py:219-220)
+ *   index[g]         int32; may be NULL
+ *   onehot[g, :]     the logits' dtype, exactly 0 or 1: the value of
+ *                    sg(onehot) + (probs - sg(probs)), outs.py:267-269; may be NULL
+ * A group holding a NaN or +inf logit, or nothing but -inf, gets index -1 and a
+ * one-hot row of NaN (a gradient of NaN); no other group is touched.  One kernel
+ * launch each:
+ *   emb_philox_uniform      out[i] = u(seed, offset, first + i), i < count, float32.
+ *   emb_onehot_sample       the index and / or the one-hot.
+ *   emb_onehot_sample_grad  grad (rows, groups, classes) in the logits' dtype from
+ *                           gout, the gradient w.r.t. the one-hot, in that dtype:
+ *                           (1 - unimix) s (gout - sum_k s_k gout_k), s = softmax(x),
+ *                           the straight-through term of outs.py:268-269; it does not
+ *                           depend on the draw.
+ * `seed` and `offset` are passed by value: a captured graph replays the draw it
+ * captured; fresh draws inside a graph come through `uniform`.
+ * EMB_ERR_INVALID before any launch: an unknown dtype or mode, rows or count < 0,
+ * groups < 1, classes outside 1 .. 256, more than 2^31 - 1 logits, unimix outside
+ * [0, 1), and with work to do a NULL logits, gout, grad or out, or index and
+ * onehot both NULL.  rows = 0 or count = 0: EMB_OK, nothing is launched.       */
+#define EMB_SAMPLE_DRAW 0
+#define EMB_SAMPLE_PRED 1
+int32_t emb_philox_uniform(uint64_t seed, uint64_t offset, uint64_t first, int64_t count, void* out, void* stream);
+int32_t emb_onehot_sample(const void* logits, int32_t dtype, int64_t rows, int64_t groups, int64_t classes,
+                          float unimix, int32_t mode, uint64_t seed, uint64_t offset, const void* uniform,
+                          void* index, void* onehot, void* stream);
+int32_t emb_onehot_sample_grad(const void* logits, const void* gout, int32_t dtype, int64_t rows, int64_t groups,
+                               int64_t classes, float unimix, void* grad, void* stream);
+/* Kernel launches the three entry points above have issued in this process,
+ * counted where the kernels are launched.                                      */
+int32_t emb_onehot_sample_launches(int64_t* count);
 
 /* ----------------------------------------------------------- collectives --
  * The two exchange steps of the sharded path on RCCL directly (xGMI inside one
