@@ -25,6 +25,7 @@ U8, I8, I16, I32, I64, F16, BF16, F32, F64, BOOL = range(10)
 LAYOUT_SAME, LAYOUT_CHANNELS_FIRST = 0, 1
 MODES = {'train': 0, 'report': 1, 'eval': 2}
 NORM_NONE, NORM_MEANSTD, NORM_PERC = 0, 1, 2
+EMB_RECON_MSE, EMB_RECON_MSE_SYMLOG, EMB_RECON_SIGMOID_MSE, EMB_RECON_BINARY = 0, 1, 2, 3
 
 
 class EmbError(RuntimeError):
@@ -227,6 +228,9 @@ SIGNATURES = {
     'emb_onehot_sample': [p, i32, i64, i64, i64, f32, i32, u64, u64, p, p, p, p],
     'emb_onehot_sample_grad': [p, p, i32, i64, i64, i64, f32, p, p],
     'emb_onehot_sample_launches': [p],
+    'emb_recon_loss': [p, i32, p, i32, f32, i64, i64, i32, p, p],
+    'emb_recon_loss_grad': [p, i32, p, i32, f32, i64, i64, i32, p, p, p],
+    'emb_recon_loss_launches': [p],
     'emb_synth_env_step': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p],
     'emb_synth_env_step_masked': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p, p, i64, i32, p],
     'emb_env_mask_supported': [i64, i32],

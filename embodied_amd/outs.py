@@ -1086,3 +1086,251 @@ def policy_loss(logits, act, adv, weight, actent=3e-4, unimix=0.0, dims=0, drop_
   ent = _composed_cat_entropy(dist, dims)
   loss = weight * -(logpi * adv + actent * ent)
   return {'loss': loss, 'logpi': logpi.detach(), 'ent': ent.detach()}
+
+
+# ---- the reconstruction heads: image MSE from uint8, symlog MSE, Binary ----------
+
+# What the kernels take: indices are 32-bit.  Structural, not a crossover; what
+# `fused=None` does with it is written beside `_recon_path`.
+RECON_MAX_ELEMENTS = 2 ** 31 - 1
+_RECON_TARGETS = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.uint8: _lib.U8}
+
+
+def recon_loss_launches():
+  """Kernel launches `emb_recon_loss` and `emb_recon_loss_grad` have issued in
+  this process."""
+  count = C.c_int64(0)
+  api.emb_recon_loss_launches(C.byref(count))
+  return count.value
+
+
+def _recon_path(who, fused, rows, units):
+  """True: the kernels, False: the composed path (`ImageMSE` says when).  The
+  kernels' median was below the composed path's at all 18 rows of
+  profiles/recon_loss_bench.txt (images (1024, 64, 64, 3) and (4096, 64, 64, 3) in
+  bfloat16 and float32 and (1024, 96, 96, 3), symlog vectors (1024, 1024) and
+  (1024, 7), the continue head (1024,) and (16384,), forward and forward +
+  backward) -- the image loss at (1024, 64, 64, 3) bfloat16: forward 24.8 us
+  against 115.3, forward + backward 122.8 against 210.0; the closest, symlog
+  (1024, 1024): 16.6 / 37.3 and 70.5 / 94.2 -- so `fused=None` takes them wherever
+  they fit and no size constant sits here.  Below about a megabyte the fused
+  forward is the host's enqueue, about 16.5 us whatever the size."""
+  fits = units >= 1 and rows * units <= RECON_MAX_ELEMENTS
+  if fused and not fits:
+    raise ValueError(
+        f'{who}(fused=True): {rows} x {units} elements, the kernels index 1 .. 2^31 - 1 '
+        '(fused=None or False composes it)')
+  if fused is None:
+    return fits
+  return bool(fused)
+
+
+def _recon_geometry(who, x, dims):
+  """(lead, rows, units) of summing the last `dims` axes of `x`."""
+  if isinstance(dims, bool) or not isinstance(dims, (int, np.integer)) or not 0 <= dims <= x.dim():
+    raise ValueError(f'{who}: dims = {dims!r}, needs 0 .. {x.dim()} for a shape of {tuple(x.shape)}')
+  lead = x.shape[:x.dim() - dims]
+  return lead, int(np.prod(lead, dtype=np.int64)), int(np.prod(x.shape[x.dim() - dims:], dtype=np.int64))
+
+
+def _recon_input(who, x, name='x'):
+  _check_device(x)
+  if x.dtype not in _DTYPES:
+    raise TypeError(f'{who}: {name} must be float32 or bfloat16, got {x.dtype}')
+
+
+def _recon_target(who, target, x, kinds):
+  """`target` on the device of `x` in a dtype the launch takes, shaped like `x`; a constant."""
+  if not torch.is_tensor(target):
+    target = torch.as_tensor(np.asarray(target))
+  if tuple(target.shape) != tuple(x.shape):
+    raise ValueError(f'{who}: target of shape {tuple(target.shape)}, needs {tuple(x.shape)}')
+  if target.dtype not in kinds:
+    raise TypeError(f'{who}: target must be one of {", ".join(str(k) for k in kinds)}, got {target.dtype}')
+  return target.detach().to(x.device)
+
+
+class _FusedRecon(torch.autograd.Function):
+  """The row sums on the kernels: one launch forward, one launch backward."""
+
+  @staticmethod
+  def forward(ctx, x, target, op, div, geometry):
+    lead, rows, units = geometry
+    xc = x.detach().contiguous()
+    target = target.contiguous()
+    if target.dtype == torch.bool:
+      target = target.view(torch.uint8)
+    loss = _lib.empty((rows,), torch.float32, x.device)
+    args = (xc.data_ptr(), _DTYPES[xc.dtype], target.data_ptr(), _RECON_TARGETS[target.dtype], div, rows, units, op)
+    api.emb_recon_loss(*args, loss.data_ptr(), _lib.raw_stream(x.device))
+    ctx.saved = (xc, target, args, lead, x.shape)
+    ctx.set_materialize_grads(False)
+    return loss.view(lead)
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    if gout is None:
+      return (None,) * 5
+    xc, target, args, lead, shape = ctx.saved
+    gout = gout.to(torch.float32).expand(lead).contiguous()
+    grad = torch.empty_like(xc)
+    api.emb_recon_loss_grad(*args, gout.data_ptr(), grad.data_ptr(), _lib.raw_stream(xc.device))
+    return (grad.view(shape),) + (None,) * 4
+
+
+def _agg(loss, dims):
+  """outs.py:56-58, `Agg.loss` with `jnp.sum` over the last `dims` axes."""
+  return loss.sum(tuple(range(-dims, 0))) if dims else loss
+
+
+def _symlog(x):
+  """nets.py symlog."""
+  return torch.sign(x) * torch.log1p(torch.abs(x))
+
+
+class MSE:
+  """The reference's `Agg(MSE(mean, squash), dims, sum)` (outs.py:40-58, 129-141;
+  `symlog_mse`: heads.py:127-130) over `mean`, a CUDA tensor of float32 or
+  bfloat16.  `squash` is None or 'symlog' (nets.py symlog, applied to the target).
+  The reference computes in float32 (outs.py:132) and so does this; a bfloat16
+  mean is widened in registers and its gradient comes back in bfloat16.
+
+  Two paths, as `TwoHot`: composed restates the reference operation by operation
+  in torch (the definition, every size); fused is `emb_recon_loss` /
+  `emb_recon_loss_grad`, one launch forward and one backward, at most 2^31 - 1
+  elements.  `fused=None` takes the kernels where they fit, True / False force a
+  path (True raises where they do not fit, and says why).  No rows: the composed
+  path, nothing is launched.  A `mean` that is not contiguous is made contiguous
+  with one torch op.
+
+  A NaN or infinite element of `mean` makes its own row's loss and its own
+  gradient element NaN on the kernels and touches no other row (composed: what
+  the definition gives, +inf for an infinite element)."""
+
+  def __init__(self, mean, squash=None, fused=None):
+    _recon_input('MSE', mean, 'mean')
+    if squash not in (None, 'symlog'):
+      raise ValueError(f"MSE: squash = {squash!r}, needs None or 'symlog'")
+    self.mean = mean
+    self.squash = squash
+    self._fused_arg = fused
+
+  def pred(self):
+    """outs.py:135-136: the mean in float32, no gradient."""
+    return self.mean.detach().to(torch.float32)
+
+  def loss(self, target, dims=0):
+    """The squared error against `target` (float32 or bfloat16, the shape of
+    `mean`; a constant) summed over the last `dims` axes: float32, shaped as the
+    axes before them.  `dims=0` is elementwise.  Differentiable once with respect
+    to `mean`."""
+    lead, rows, units = _recon_geometry('MSE.loss', self.mean, dims)
+    target = _recon_target('MSE.loss', target, self.mean, (torch.float32, torch.bfloat16))
+    if _recon_path('MSE', self._fused_arg, rows, units) and rows > 0:
+      op = _lib.EMB_RECON_MSE_SYMLOG if self.squash else _lib.EMB_RECON_MSE
+      return _FusedRecon.apply(self.mean, target, op, 1.0, (lead, rows, units))
+    target = target.to(torch.float32)
+    if self.squash:
+      target = _symlog(target)
+    return _agg(torch.square(self.mean.to(torch.float32) - target), dims)
+
+
+class ImageMSE:
+  """The image reconstruction loss (agent.py:170-182): the decoder's last line
+  `jax.nn.sigmoid(x)` (rssm.py:349) under `Agg(MSE(out), 3, sum)` (rssm.py:353-356),
+  trained against `f32(image) / 255` (agent.py:181).  `x` is the decoder's
+  PRE-sigmoid output (..., H, W, C), a CUDA tensor of float32 or bfloat16;
+  `sigmoid=False` is the plain MSE of `x` against `image / 255`.
+
+  Two paths, as `MSE`.  On the kernels the uint8 frames are read once, widened
+  and divided by 255 in registers (the float32 division the reference writes);
+  no float copy of the batch is made, forward or backward.
+
+  One difference, as `nets.norm_act` documents its own: the reference rounds
+  sigmoid(x) to the compute dtype before `MSE` widens it again (rssm.py:349,
+  outs.py:132).  The composed path keeps that rounding; the kernels do not --
+  they take the sigmoid of the widened x in float32 and never round it.  For
+  float32 there is no difference."""
+
+  def __init__(self, x, sigmoid=True, fused=None):
+    _recon_input('ImageMSE', x)
+    self.x = x
+    self.sigmoid = bool(sigmoid)
+    self._fused_arg = fused
+
+  def pred(self):
+    """sigmoid(x) (or x) in float32, no gradient: composed torch ops, for the report path."""
+    x = self.x.detach()
+    return (torch.sigmoid(x) if self.sigmoid else x).to(torch.float32)
+
+  def loss(self, image, dims=3):
+    """The squared error against `image / 255` (uint8, the shape of `x`; a
+    constant) summed over the last `dims` axes: float32.  Differentiable once
+    with respect to `x`."""
+    lead, rows, units = _recon_geometry('ImageMSE.loss', self.x, dims)
+    image = _recon_target('ImageMSE.loss', image, self.x, (torch.uint8,))
+    if _recon_path('ImageMSE', self._fused_arg, rows, units) and rows > 0:
+      op = _lib.EMB_RECON_SIGMOID_MSE if self.sigmoid else _lib.EMB_RECON_MSE
+      return _FusedRecon.apply(self.x, image, op, 255.0, (lead, rows, units))
+    mean = torch.sigmoid(self.x) if self.sigmoid else self.x          # rssm.py:349, in the compute dtype
+    # agent.py:181 divides; torch turns a division by a Python scalar into a product with its
+    # reciprocal, which rounds k / 255 differently for some k: divide by a tensor
+    scale = torch.full((), 255.0, dtype=torch.float32, device=image.device)
+    return _agg(torch.square(mean.to(torch.float32) - image.to(torch.float32) / scale), dims)
+
+
+class Binary:
+  """The reference's `Binary` (outs.py:189-205), the continue head (agent.py:177),
+  over `logit`, a CUDA tensor of float32 or bfloat16; `dims` sums the last axes as
+  `Agg` does.  Two paths, as `MSE`; the kernels compute
+  logsigmoid(x) = min(x, 0) - log1p(exp(-|x|)), so logit = +-1e4 against the
+  wrong label costs |logit| and stays finite."""
+
+  def __init__(self, logit, fused=None):
+    _recon_input('Binary', logit, 'logit')
+    self.logit = logit
+    self._fused_arg = fused
+
+  def pred(self):
+    """outs.py:194-195."""
+    return self.logit.detach() > 0
+
+  def _event(self, who, event):
+    kinds = (torch.bool, torch.uint8, torch.float32, torch.bfloat16, torch.float16, torch.float64)
+    event = _recon_target(who, event, self.logit, kinds)
+    return event.to(torch.float32) if event.dtype in (torch.float16, torch.float64) else event
+
+  def loss(self, target, dims=0):
+    """-logp(target) (outs.py:21-22): float32, differentiable once with respect to the logit."""
+    lead, rows, units = _recon_geometry('Binary.loss', self.logit, dims)
+    target = self._event('Binary.loss', target)
+    if _recon_path('Binary', self._fused_arg, rows, units) and rows > 0:
+      return _FusedRecon.apply(self.logit, target, _lib.EMB_RECON_BINARY, 1.0, (lead, rows, units))
+    return -self._composed_logp(target, dims)
+
+  def logp(self, event, dims=0):
+    """outs.py:197-201: event * logsigmoid(logit) + (1 - event) * logsigmoid(-logit);
+    `event` is torch.bool, uint8 or a float tensor of the logit's shape."""
+    return -self.loss(event, dims)
+
+  def _composed_logp(self, event, dims):
+    logit = self.logit.to(torch.float32)
+    event = event.to(torch.float32)
+    logp = torch.nn.functional.logsigmoid(logit)
+    lognotp = torch.nn.functional.logsigmoid(-logit)
+    return _agg(event * logp + (1 - event) * lognotp, dims)
+
+  def sample(self, seed=None, offset=0, uniform=None):
+    """outs.py:203-205: `u < sigmoid(logit)`, a torch.bool tensor, with one uniform
+    per element from `philox_uniform(seed, offset)` or the caller's `uniform`
+    (float32, the logit's shape).  Composed torch ops: not a hot path."""
+    offset = _check_counter('Binary.sample', 'offset', offset)
+    logit = self.logit.detach()
+    if uniform is None:
+      seed = _check_counter('Binary.sample', 'seed', seed)
+      uniform = philox_uniform(seed, offset, 0, logit.numel(), logit.device).view(logit.shape)
+    elif not (torch.is_tensor(uniform) and uniform.dtype == torch.float32 and uniform.device == logit.device
+              and uniform.shape == logit.shape):
+      raise TypeError(f'Binary.sample: uniform must be a float32 tensor of shape {tuple(logit.shape)} on {logit.device}')
+    return uniform < torch.sigmoid(logit.to(torch.float32))

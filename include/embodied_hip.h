@@ -49,7 +49,8 @@ extern "C" {
  * emb_optim_metrics, emb_optim_launches, emb_norm_act, emb_norm_act_grad,
  * emb_norm_act_launches, emb_gru_gate, emb_gru_gate_grad, emb_gru_gate_launches,
  * emb_philox_uniform, emb_onehot_sample, emb_onehot_sample_grad,
- * emb_onehot_sample_launches (additions only).                                 */
+ * emb_onehot_sample_launches, emb_recon_loss, emb_recon_loss_grad,
+ * emb_recon_loss_launches (additions only).                                    */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -954,6 +955,43 @@ int32_t emb_onehot_sample_grad(const void* logits, const void* gout, int32_t dty
 /* Kernel launches the three entry points above have issued in this process,
  * counted where the kernels are launched.                                      */
 int32_t emb_onehot_sample_launches(int64_t* count);
+
+/* ---- the reconstruction terms of the world-model loss, float32 arithmetic on device
+ * Three terms of DreamerV3's loss (dreamerv3/agent.py:170-182) are sums of
+ * elementwise errors over the trailing `units` elements of a row:
+ *   the image loss    Agg(MSE(sigmoid(x)), 3, sum) against f32(frame) / 255
+ *                     (dreamerv3/rssm.py:349, 353-356; agent.py:181)
+ *   the vector loss   Agg(MSE(x, symlog), 1, sum)  (embodied/jax/heads.py:127-130,
+ *                     embodied/jax/outs.py:129-141, embodied/jax/nets.py symlog)
+ *   the continue head Binary(logit).loss(con)      (agent.py:177, outs.py:189-201)
+ * under Agg (outs.py:40-58).  `x` is (rows, units) contiguous on device, EMB_F32 or
+ * EMB_BF16; `target` the same shape in EMB_F32, EMB_BF16 or EMB_U8.  Per element
+ * t = float32(target) / div in float32 (div = 255 for frames, 1 otherwise), and
+ * with s(x) = 1 / (1 + exp(-x)), ls(x) = min(x, 0) - log1p(exp(-|x|)), g = gout[row]:
+ *   EMB_RECON_MSE          loss = sum (x - t)^2                 grad = 2 (x - t) g
+ *   EMB_RECON_MSE_SYMLOG   loss = sum (x - sign(t) log1p|t|)^2  grad = 2 (x - symlog t) g
+ *   EMB_RECON_SIGMOID_MSE  loss = sum (s(x) - t)^2              grad = 2 (s(x) - t) s(x) (1 - s(x)) g
+ *   EMB_RECON_BINARY       loss = sum -(t ls(x) + (1 - t) ls(-x))   grad = (s(x) - t) g
+ * One kernel launch each, no atomics, the same bits from run to run and whatever
+ * the alignment of the pointers:
+ *   emb_recon_loss       loss (rows,) float32, each row summed in a fixed order.
+ *   emb_recon_loss_grad  grad (rows, units) in the dtype of x from gout (rows,) float32.
+ * A NaN or infinite x makes its own row's loss and its own gradient element NaN
+ * and touches no other row.  Pointers may start on any multiple of their element
+ * size.  EMB_ERR_INVALID before any launch: an unknown dtype or op, div not
+ * positive and finite, rows < 0, units < 1, more than 2^31 - 1 elements, and with
+ * work to do a NULL or misaligned pointer.  rows = 0: EMB_OK, nothing is launched. */
+#define EMB_RECON_MSE 0
+#define EMB_RECON_MSE_SYMLOG 1
+#define EMB_RECON_SIGMOID_MSE 2
+#define EMB_RECON_BINARY 3
+int32_t emb_recon_loss(const void* x, int32_t x_dtype, const void* target, int32_t target_dtype, float div,
+                       int64_t rows, int64_t units, int32_t op, void* loss, void* stream);
+int32_t emb_recon_loss_grad(const void* x, int32_t x_dtype, const void* target, int32_t target_dtype, float div,
+                            int64_t rows, int64_t units, int32_t op, const void* gout, void* grad, void* stream);
+/* Kernel launches the two entry points above have issued in this process,
+ * counted where the kernels are launched.                                      */
+int32_t emb_recon_loss_launches(int64_t* count);
 
 /* ----------------------------------------------------------- collectives --
  * The two exchange steps of the sharded path on RCCL directly (xGMI inside one
