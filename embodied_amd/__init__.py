@@ -38,6 +38,7 @@ from .outs import OneHot, rssm_kl, onehot_kl_launches
 from .outs import Categorical, policy_loss, policy_loss_launches
 from .outs import philox_uniform, onehot_sample_launches
 from .outs import MSE, ImageMSE, Binary, recon_loss_launches
+from .outs import Normal, normal_policy_loss, philox_normal, normal_policy_launches
 from . import nets
 from .nets import NormAct, norm_act, gru_gate, norm_act_launches, gru_gate_launches
 from . import optim

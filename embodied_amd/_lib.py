@@ -26,6 +26,7 @@ LAYOUT_SAME, LAYOUT_CHANNELS_FIRST = 0, 1
 MODES = {'train': 0, 'report': 1, 'eval': 2}
 NORM_NONE, NORM_MEANSTD, NORM_PERC = 0, 1, 2
 EMB_RECON_MSE, EMB_RECON_MSE_SYMLOG, EMB_RECON_SIGMOID_MSE, EMB_RECON_BINARY = 0, 1, 2, 3
+NORMAL_BOUNDED, NORMAL_LOGSTD = 0, 1
 
 
 class EmbError(RuntimeError):
@@ -231,6 +232,11 @@ SIGNATURES = {
     'emb_recon_loss': [p, i32, p, i32, f32, i64, i64, i32, p, p],
     'emb_recon_loss_grad': [p, i32, p, i32, f32, i64, i64, i32, p, p, p],
     'emb_recon_loss_launches': [p],
+    'emb_normal_policy_loss': [p, p, p, i32, i64, i64, i32, i64, i32, f32, f32, f32, p, p, i64, p, p, p, p],
+    'emb_normal_policy_loss_grad': [p, p, p, i32, i64, i64, i32, i64, i32, f32, f32, f32, p, p, i64, p, p, p, p],
+    'emb_normal_sample': [p, p, i32, i64, i64, i32, f32, f32, u64, u64, p, p, p],
+    'emb_philox_normal': [u64, u64, u64, i64, p, p],
+    'emb_normal_policy_launches': [p],
     'emb_synth_env_step': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p],
     'emb_synth_env_step_masked': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p, p, i64, i32, p],
     'emb_env_mask_supported': [i64, i32],

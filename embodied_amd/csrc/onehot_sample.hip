@@ -23,6 +23,7 @@
 // an address.  No atomics, no traffic between waves: the same bits run to run.
 #include "onehot_sample.h"
 #include "onehot_segment.h"
+#include "philox.h"
 
 #include <atomic>
 
@@ -42,22 +43,7 @@ static_assert(kWave == kLanes, "the segment helpers shuffle over one wave64");
 
 // Philox4x32-10, word 0 of the block at counter (g, offset) under key seed.
 __device__ __forceinline__ uint32_t philox_word0(uint64_t seed, uint64_t offset, uint64_t g) {
-  constexpr uint32_t kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u, kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
-  uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
-  uint32_t c0 = static_cast<uint32_t>(g), c1 = static_cast<uint32_t>(g >> 32);
-  uint32_t c2 = static_cast<uint32_t>(offset), c3 = static_cast<uint32_t>(offset >> 32);
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const uint32_t hi0 = __umulhi(kM0, c0), lo0 = kM0 * c0;
-    const uint32_t hi1 = __umulhi(kM1, c2), lo1 = kM1 * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += kW0;
-    k1 += kW1;
-  }
-  return c0;
+  return philox::block(seed, offset, g).word[0];              // the ten rounds: philox.h
 }
 
 __device__ __forceinline__ float to_uniform(uint32_t word) {

@@ -3,9 +3,12 @@ value networks (embodied/jax/heads.py:132-144, embodied/jax/outs.py:273-330),
 the one-hot latents' KL pair of its world model (`OneHot`, `rssm_kl`:
 dreamerv3/rssm.py:123-132, embodied/jax/outs.py:40-76, 208-263), the
 actor's discrete policy head and loss (`Categorical`, `policy_loss`:
-dreamerv3/agent.py:411-415, embodied/jax/outs.py:208-240), and the draw of
+dreamerv3/agent.py:411-415, embodied/jax/outs.py:208-240), the draw of
 both (`OneHot.sample` / `pred`, `Categorical.sample`: dreamerv3/rssm.py:87, 100,
-dreamerv3/agent.py:18, 126, 192, embodied/jax/outs.py:219-224, 248-254, 265-270).
+dreamerv3/agent.py:18, 126, 192, embodied/jax/outs.py:219-224, 248-254, 265-270),
+the reconstruction heads (`MSE`, `ImageMSE`, `Binary`), and the actor's
+continuous policy head, its loss and its draw (`Normal`, `normal_policy_loss`:
+embodied/jax/heads.py:146-162, embodied/jax/outs.py:161-186).
 
 It sits on both sides of `scans.dreamer_targets`: that function's `pred`
 argument is `value.pred()` / `slowvalue.pred()` and its `tar_padded` result goes
@@ -1334,3 +1337,353 @@ class Binary:
               and uniform.shape == logit.shape):
       raise TypeError(f'Binary.sample: uniform must be a float32 tensor of shape {tuple(logit.shape)} on {logit.device}')
     return uniform < torch.sigmoid(logit.to(torch.float32))
+
+
+# ---- Normal: the actor's continuous policy, its logp, entropy, loss and draw ----
+
+# What the kernels take: a row of at most 256 action dimensions stays in one
+# wave's registers, indices are 32-bit.  Structural, not a crossover: the fused
+# median is below the composed one at all 48 rows of profiles/normal_policy_bench.txt
+# (N 1024 and 16 384, T 16, A 1, 6, 21 and 38, float32 and bfloat16, forward,
+# forward + backward and sample), so no size constant sits beside `_normal_path`;
+# the figures are quoted there.
+NORMAL_MAX_ACTIONS = 256
+NORMAL_MAX_ELEMENTS = 2 ** 31 - 1
+_NORMAL_KINDS = {'bounded': _lib.NORMAL_BOUNDED, 'logstd': _lib.NORMAL_LOGSTD}
+_HALF_LOG_2PI = float(np.float32(0.5 * np.log(2 * np.pi)))
+_TWO_PI = float(np.float32(2 * np.pi))
+
+
+def normal_policy_launches():
+  """Kernel launches `emb_normal_policy_loss`, `emb_normal_policy_loss_grad`,
+  `emb_normal_sample` and `emb_philox_normal` have issued in this process."""
+  count = C.c_int64(0)
+  api.emb_normal_policy_launches(C.byref(count))
+  return count.value
+
+
+def philox_normal(seed, offset=0, first=0, count=1, device=None):
+  """(count,) float32 on `device`: the standard normals the sample kernel draws
+  for the elements `first .. first + count - 1` -- the Philox4x32-10 block keyed as
+  `philox_uniform`'s, u1 = ((word 0 >> 8) + 1) * 2^-24 in (0, 1], u2 = (word 1 >> 8) *
+  2^-24, eps = sqrt(-2 ln u1) cos(2 pi u2).  One launch (`emb_philox_normal`);
+  count = 0 launches nothing."""
+  seed = _check_counter('philox_normal', 'seed', seed)
+  offset = _check_counter('philox_normal', 'offset', offset)
+  first = _check_counter('philox_normal', 'first', first)
+  count = int(count)
+  if count < 0 or first + count > 2 ** 64:
+    raise ValueError(f'philox_normal: count = {count} from first = {first}, needs 0 <= count and elements below 2^64')
+  device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+  if device.type != 'cuda':
+    raise RuntimeError('embodied_amd.outs runs as HIP kernels: pass a CUDA device (no CPU fallback)')
+  out = torch.empty((count,), dtype=torch.float32, device=device)
+  if count:
+    api.emb_philox_normal(seed, offset, first, count, out.data_ptr(), _lib.raw_stream(out.device))
+  return out
+
+
+def _normal_path(fused, rows, actions):
+  """True: the kernels, False: the composed path (`normal_policy_loss` says
+  when); `rows` counts the inputs' rows, a dropped step's included.  The
+  kernels' median was below the composed path's at every shape, dtype and piece
+  measured (profiles/normal_policy_bench.txt) -- the closest, (16384, 16, 38)
+  bf16: forward 102.0 us against 343.6, forward + backward 231.6 against 795.8,
+  sample 47.7 against 156.2; (1024, 16, 6) f32: 23.0 / 126.4, 95.1 / 392.0 and 12.5 /
+  43.2 -- so `fused=None` takes them wherever they fit.  Up to (16384, 16, 6) the
+  fused figures are the host's enqueue (23 us forward, 95 with autograd's
+  backward, 12.5 for the sample) whatever the size."""
+  fits = 1 <= actions <= NORMAL_MAX_ACTIONS and rows * actions <= NORMAL_MAX_ELEMENTS
+  if fused and not 1 <= actions <= NORMAL_MAX_ACTIONS:
+    raise ValueError(
+        f'Normal(fused=True): {actions} action dimensions, the kernels keep a row of at most {NORMAL_MAX_ACTIONS} in '
+        'one wave\'s registers (fused=None or False composes it)')
+  if fused and not fits:
+    raise ValueError(
+        f'Normal(fused=True): {rows} x {actions} elements, the kernels index 1 .. 2^31 - 1 '
+        '(fused=None or False composes it)')
+  if fused is None:
+    return fits
+  return bool(fused)
+
+
+def _check_normal(who, mean_raw, std_raw, kind, minstd, maxstd, dims):
+  """(kind id, lo, hi) with lo and hi the float32 values the kernels are handed."""
+  _check_device(mean_raw)
+  _check_device(std_raw)
+  if mean_raw.dtype not in _DTYPES:
+    raise TypeError(f'{who}: mean_raw must be float32 or bfloat16, got {mean_raw.dtype}')
+  if std_raw.dtype != mean_raw.dtype or std_raw.device != mean_raw.device:
+    raise TypeError(f'{who}: mean_raw is {mean_raw.dtype} on {mean_raw.device}, std_raw {std_raw.dtype} on '
+                    f'{std_raw.device}')
+  if std_raw.shape != mean_raw.shape:
+    raise ValueError(f'{who}: mean_raw of shape {tuple(mean_raw.shape)}, std_raw of {tuple(std_raw.shape)}')
+  if kind not in _NORMAL_KINDS:
+    raise ValueError(f"{who}: kind = {kind!r}, needs 'bounded' or 'logstd'")
+  if dims not in (0, 1):
+    raise ValueError(f'{who}: dims = {dims!r}, needs 0 (...) or 1 (..., actions); '
+                     'flatten more action dimensions into the last axis')
+  if mean_raw.dim() < dims or (dims and mean_raw.shape[-1] < 1):
+    raise ValueError(f'{who}: inputs of shape {tuple(mean_raw.shape)}, needs (..., actions)')
+  lo, hi = float(np.float32(minstd)), float(np.float32(maxstd))
+  if kind == 'bounded' and not (0.0 < lo <= hi and np.isfinite(hi)):
+    raise ValueError(f'{who}: minstd = {minstd}, maxstd = {maxstd}, bounded needs finite maxstd >= minstd > 0')
+  return _NORMAL_KINDS[kind], lo, hi
+
+
+def _normal_actions(who, act, like):
+  """`act` as float32 on the inputs' device, shaped like them; a constant."""
+  if not torch.is_tensor(act):
+    act = torch.as_tensor(np.asarray(act))
+  if not act.dtype.is_floating_point:
+    raise TypeError(f'{who}: actions must be floating point (outs.py:175), got {act.dtype}')
+  if act.shape != like.shape:
+    raise ValueError(f'{who}: actions of shape {tuple(act.shape)}, the inputs need {tuple(like.shape)}')
+  return act.detach().to(device=like.device, dtype=torch.float32).contiguous()
+
+
+def _normal_moments(mean_raw, std_raw, kind, lo, hi):
+  """heads.py:150-152 (`bounded_normal`) or heads.py:161 (`normal_logstd`) in
+  float32 (outs.py:164-165): (mean, stddev)."""
+  m, s = mean_raw.to(torch.float32), std_raw.to(torch.float32)
+  if kind == _lib.NORMAL_BOUNDED:
+    span = float(np.float32(hi) - np.float32(lo))
+    return torch.tanh(m), span * torch.sigmoid(s + 2.0) + lo
+  return m, torch.exp(s)
+
+
+def _composed_normal_logp(mean, std, act, dims):
+  """outs.py:174-176 under `Agg.logp` (outs.py:63-64)."""
+  z = (act - mean) / std
+  logp = -(z * z) * 0.5 - torch.log(std) - _HALF_LOG_2PI
+  return logp.sum(-1) if dims else logp
+
+
+def _composed_normal_entropy(std, dims):
+  """outs.py:178-179 under `Agg.entropy` (outs.py:69-71)."""
+  entropy = 0.5 * torch.log(_TWO_PI * (std * std)) + 0.5
+  return entropy.sum(-1) if dims else entropy
+
+
+class _FusedNormalPolicy(torch.autograd.Function):
+  """(loss, logpi, ent), each (N * (T - drop),) float32, on the kernels: one
+  launch forward, one backward.  Only `loss` carries a gradient, to both raw inputs."""
+
+  @staticmethod
+  def forward(ctx, mean_raw, std_raw, act, adv, weight, stride, geometry, head, actent):
+    n, t, drop, actions = geometry
+    m, s = mean_raw.detach().contiguous(), std_raw.detach().contiguous()
+    dtype = _DTYPES[m.dtype]
+    loss, logpi, ent = _lib.empty((3, n * (t - drop)), torch.float32, m.device).unbind(0)
+    address = lambda tensor: None if tensor is None else tensor.data_ptr()
+    api.emb_normal_policy_loss(
+        m.data_ptr(), s.data_ptr(), address(act), dtype, n, t, drop, actions, *head, actent, address(adv),
+        address(weight), stride, loss.data_ptr(), logpi.data_ptr(), ent.data_ptr(), _lib.raw_stream(m.device))
+    ctx.saved = (m, s, act, adv, weight, stride, geometry, head, actent, dtype, mean_raw.shape)
+    ctx.set_materialize_grads(False)
+    ctx.mark_non_differentiable(logpi, ent)
+    return loss, logpi, ent
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout, _logpi, _ent):
+    if gout is None:
+      return (None,) * 9
+    m, s, act, adv, weight, stride, geometry, head, actent, dtype, shape = ctx.saved
+    n, t, drop, actions = geometry
+    gout = gout.to(torch.float32).contiguous()
+    grad_mean, grad_std = torch.empty_like(m), torch.empty_like(s)
+    address = lambda tensor: None if tensor is None else tensor.data_ptr()
+    api.emb_normal_policy_loss_grad(
+        m.data_ptr(), s.data_ptr(), address(act), dtype, n, t, drop, actions, *head, actent, address(adv),
+        address(weight), stride, gout.data_ptr(), grad_mean.data_ptr(), grad_std.data_ptr(), _lib.raw_stream(m.device))
+    return (grad_mean.view(shape), grad_std.view(shape)) + (None,) * 7
+
+
+class Normal:
+  """The reference's `Agg(Normal(mean, stddev), dims, sum)` (outs.py:40-76, 161-186)
+  as `Head.bounded_normal` and `Head.normal_logstd` build it (heads.py:146-162),
+  the continuous policy head, over the two linear layers' raw outputs
+  `mean_raw` and `std_raw`, CUDA tensors of float32 or bfloat16 (both the same):
+
+    kind='bounded'  mean = tanh(mean_raw), stddev = (maxstd - minstd) sigmoid(std_raw + 2) + minstd
+    kind='logstd'   mean = mean_raw,       stddev = exp(std_raw)
+    dims=0          inputs and actions (...): a scalar action per row
+    dims=1          inputs and actions (..., actions), `logp` and `entropy` summed over
+                    the last axis; more action axes are flattened into it by the caller
+
+  `.logp(act)` and `.entropy()` are (...) float32 and differentiable once with
+  respect to both raw inputs; `.pred()` is the mean (composed torch ops, no
+  gradient); `.sample(seed)` draws float32 actions without a gradient (`imag_loss`
+  takes `sg(act)`, and no loss of the reference uses the reparameterised gradient).
+  `.minent` and `.maxent` are heads.py:153-154 summed over the actions, what
+  agent.py:440-442 reads (None for 'logstd', which sets neither).  `.kl` is not
+  part of this.
+
+  Two paths, as `Categorical`: composed restates the reference line by line in
+  torch (the definition, every size); fused is `emb_normal_policy_loss` /
+  `emb_normal_policy_loss_grad` / `emb_normal_sample`, at most 256 actions, one
+  launch per call and one per backward.  `fused=None` takes the kernels where
+  they fit, True / False force a path (True raises where they do not fit, and says
+  why).  No rows: the composed path, nothing is launched.  `normal_policy_loss`
+  documents the arithmetic and the non-finite inputs."""
+
+  def __init__(self, mean_raw, std_raw, kind='bounded', minstd=1.0, maxstd=1.0, dims=1, fused=None):
+    self._head = _check_normal('Normal', mean_raw, std_raw, kind, minstd, maxstd, dims)
+    self.mean_raw, self.std_raw = mean_raw, std_raw
+    self.kind, self.dims = kind, dims
+    self._lead = mean_raw.shape[:mean_raw.dim() - dims]
+    self._actions = mean_raw.shape[-1] if dims else 1
+    self._rows = int(np.prod(self._lead, dtype=np.int64))
+    self.fused = _normal_path(fused, self._rows, self._actions) and self._rows > 0
+    if kind == 'bounded':
+      _, lo, hi = self._head
+      entropy = lambda std: (0.5 * float(np.log(2 * np.pi * std * std)) + 0.5) * self._actions
+      self.minent, self.maxent = entropy(lo), entropy(hi)
+    else:
+      self.minent = self.maxent = None
+
+  def _moments(self):
+    return _normal_moments(self.mean_raw, self.std_raw, *self._head)
+
+  def _launch(self, act, actent):
+    geometry = (self._rows, 1, 0, self._actions)
+    loss = _FusedNormalPolicy.apply(self.mean_raw, self.std_raw, act, None, None, 1, geometry, self._head, actent)[0]
+    return loss.view(self._lead)
+
+  def pred(self):
+    """outs.py:167-168: the mean, float32, shaped like the inputs."""
+    with torch.no_grad():
+      return self._moments()[0]
+
+  def sample(self, seed=None, offset=0, eps=None):
+    """outs.py:170-172: `mean + stddev * eps`, float32, shaped like the inputs, no
+    gradient -- what `logp` and `normal_policy_loss` take as `act`.  `eps` is one
+    standard normal per element from `philox_normal(seed, offset)`: element e of
+    the flattened inputs takes the Philox block at counter (e, `offset`) under
+    key `seed`, so the noise depends on (seed, offset, e) alone, not on the dtype,
+    the path or the launch geometry.  `seed` and `offset` are integers in
+    [0, 2^64) and travel to the kernel by value: a replayed graph repeats the
+    draw it captured.  `eps`, a float32 tensor shaped like the inputs, replaces
+    the counter and is read anew on every replay.  On the kernels ONE launch;
+    composed draws the same noise with `emb_philox_normal` and uses torch ops."""
+    who = 'Normal.sample'
+    offset = _check_counter(who, 'offset', offset)
+    like = self.mean_raw
+    if eps is None:
+      seed = _check_counter(who, 'seed', seed)
+    else:
+      seed = 0 if seed is None else _check_counter(who, 'seed', seed)
+      if not (torch.is_tensor(eps) and eps.dtype == torch.float32 and eps.device == like.device):
+        raise TypeError(f'{who}: eps must be a float32 tensor on {like.device}')
+      if eps.shape != like.shape:
+        raise ValueError(f'{who}: eps of shape {tuple(eps.shape)}, needs {tuple(like.shape)}')
+      eps = eps.detach().contiguous()
+    count = self._rows * self._actions
+    if self.fused and count > 0:
+      m, s = self.mean_raw.detach().contiguous(), self.std_raw.detach().contiguous()
+      act = torch.empty(like.shape, dtype=torch.float32, device=like.device)
+      api.emb_normal_sample(
+          m.data_ptr(), s.data_ptr(), _DTYPES[m.dtype], self._rows, self._actions, *self._head, seed, offset,
+          None if eps is None else eps.data_ptr(), act.data_ptr(), _lib.raw_stream(like.device))
+      return act
+    with torch.no_grad():
+      if eps is None:
+        eps = philox_normal(seed, offset, 0, count, like.device).view(like.shape)
+      mean, std = self._moments()
+      return mean + std * eps
+
+  def logp(self, act):
+    """(...) float32: the log-density of `act` (any floating dtype; a constant)."""
+    act = _normal_actions('Normal.logp', act, self.mean_raw)
+    if self.fused:
+      return -self._launch(act, 0.0)              # the launch's loss with adv = weight = 1, actent = 0 is -logp
+    mean, std = self._moments()
+    return _composed_normal_logp(mean, std, act, self.dims)
+
+  def entropy(self):
+    """(...) float32."""
+    if self.fused:
+      return self._launch(None, -1.0)             # no action and actent = -1: the launch's loss is the entropy
+    return _composed_normal_entropy(self._moments()[1], self.dims)
+
+
+def normal_policy_loss(mean_raw, std_raw, act, adv, weight, actent=3e-4, kind='bounded', minstd=0.1, maxstd=1.0,
+                       dims=1, drop_last=True, fused=None):
+  """The actor's loss of `imag_loss` (agent.py:411-415) for one continuous action key:
+
+      logpi = policy.logp(sg(act))[:, :-1]
+      ent   = policy.entropy()[:, :-1]
+      loss  = sg(weight[:, :-1]) * -(logpi * sg(adv) + actent * ent)
+
+  with policy = `Normal(mean_raw, std_raw, kind, minstd, maxstd, dims)`, as a dict
+  of three float32 tensors.  Per element, in float32,
+
+      z = (act - mean) / std
+      logp_a = -z^2 / 2 - log(std) - log(2 pi) / 2        ent_a = log(2 pi std^2) / 2 + 1 / 2
+
+  `loss` is differentiable once with respect to both raw inputs and to nothing
+  else: `act`, `adv` and `weight` are constants, the reference's `sg`.  `logpi`
+  and `ent` carry no gradient; they are for `metrics['ent/...']` (agent.py:438-442).
+
+  The inputs are (N.., T[, actions]) and `act` has their shape, in any floating
+  dtype (converted to float32; integers raise TypeError).  With `drop_last` the
+  last step of every sequence is dropped, the reference's `[:, :-1]`: the outputs
+  and `adv` are (N.., T - 1), and `weight` is (N.., T) as `scans.dreamer_targets`
+  returns it or (N.., T - 1).  Without it all three are the leading shape of the
+  inputs, whatever its rank.  The kernels read the kept rows in place: nothing is
+  sliced or copied and a dropped step is not read.
+
+  Two paths, as `Normal`.  On the kernels that is ONE launch forward and ONE
+  backward, whose closed form takes 1 - tanh^2(m) from exp(-2 |m|) (autograd's
+  1 - tanh(m)^2 loses digits from |m| of about 5 on).  No output rows (N = 0, or
+  T = 1 with `drop_last`): nothing is launched and the gradient is zeros.
+
+  Non-finite inputs.  A NaN in `mean_raw`, `std_raw` or `act` of a kept step
+  makes that output row's `loss`, `logpi` and `ent` and its gradient rows NaN on
+  the kernels and touches no other row; composed is the definition: `logpi` and
+  `loss` are NaN, `ent` is where the NaN is in `std_raw` (the entropy does not
+  read the mean or the action), and the gradient is what autograd leaves.  The
+  same values in a dropped step touch nothing: every output has the bits of the
+  clean run and that step's gradient is zeros.  'bounded' stays finite for raw
+  values of +-1e4: the stddev is the formula's value at sigmoid = 0 or 1 and the
+  gradient to `mean_raw` is exactly 0 on the kernels.  'logstd' returns what the
+  float32 definition returns when `exp` overflows (+-inf or NaN), confined to the row."""
+  head = _check_normal('normal_policy_loss', mean_raw, std_raw, kind, minstd, maxstd, dims)
+  actent = float(actent)
+  if not np.isfinite(actent):
+    raise ValueError(f'normal_policy_loss: actent = {actent}, needs a finite value')
+  lead = mean_raw.shape[:mean_raw.dim() - dims]
+  actions = mean_raw.shape[-1] if dims else 1
+  drop = 1 if drop_last else 0
+  if drop and not lead:
+    raise ValueError(f'normal_policy_loss: drop_last needs a time axis, inputs of shape {tuple(mean_raw.shape)}')
+  n, t = (int(np.prod(lead[:-1], dtype=np.int64)), lead[-1]) if drop else (int(np.prod(lead, dtype=np.int64)), 1)
+  kept = max(t - drop, 0)
+  out_shape = (*lead[:-1], kept) if drop else tuple(lead)
+  act = _normal_actions('normal_policy_loss', act, mean_raw)
+
+  def constant(name, value, shapes):
+    if not torch.is_tensor(value):
+      value = torch.as_tensor(np.asarray(value, np.float32))
+    if tuple(value.shape) not in shapes:
+      raise ValueError(f'normal_policy_loss: {name} of shape {tuple(value.shape)}, needs ' +
+                       ' or '.join(str(tuple(s)) for s in shapes))
+    return value.detach().to(device=mean_raw.device, dtype=torch.float32).contiguous()
+
+  adv = constant('adv', adv, (out_shape,))
+  weight = constant('weight', weight, (out_shape, tuple(lead)))
+  if _normal_path(fused, n * t, actions) and n * kept > 0:
+    stride = weight.shape[-1] if drop else 1
+    loss, logpi, ent = _FusedNormalPolicy.apply(
+        mean_raw, std_raw, act, adv, weight, stride, (n, t, drop, actions), head, actent)
+    return {'loss': loss.view(out_shape), 'logpi': logpi.view(out_shape), 'ent': ent.view(out_shape)}
+  if drop:      # the reference's [:, :-1], taken before the arithmetic instead of after: a dropped step takes no part
+    axis = len(lead) - 1
+    mean_raw, std_raw, act = (x.narrow(axis, 0, kept) for x in (mean_raw, std_raw, act))
+    weight = weight[..., :kept]
+  mean, std = _normal_moments(mean_raw, std_raw, *head)
+  logpi = _composed_normal_logp(mean, std, act, dims)
+  ent = _composed_normal_entropy(std, dims)
+  loss = weight * -(logpi * adv + actent * ent)
+  return {'loss': loss, 'logpi': logpi.detach(), 'ent': ent.detach()}

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports (139 functions). */
+ * it exports (144 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -50,7 +50,9 @@ extern "C" {
  * emb_norm_act_launches, emb_gru_gate, emb_gru_gate_grad, emb_gru_gate_launches,
  * emb_philox_uniform, emb_onehot_sample, emb_onehot_sample_grad,
  * emb_onehot_sample_launches, emb_recon_loss, emb_recon_loss_grad,
- * emb_recon_loss_launches (additions only).                                    */
+ * emb_recon_loss_launches, emb_normal_policy_loss, emb_normal_policy_loss_grad,
+ * emb_normal_sample, emb_philox_normal, emb_normal_policy_launches (additions
+ * only).                                                                       */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -992,6 +994,76 @@ int32_t emb_recon_loss_grad(const void* x, int32_t x_dtype, const void* target, 
 /* Kernel launches the two entry points above have issued in this process,
  * counted where the kernels are launched.                                      */
 int32_t emb_recon_loss_launches(int64_t* count);
+
+/* ---- the continuous policy head: Normal logp, entropy, policy loss and draw on device
+ * The actor's loss of DreamerV3's imagination (dreamerv3/agent.py:411-415) for a
+ * continuous action key, whose policy is Agg(Normal(mean, stddev), dims, sum)
+ * (embodied/jax/outs.py:40-76 Agg, 161-186 Normal) as Head.bounded_normal and
+ * Head.normal_logstd build it (embodied/jax/heads.py:146-162).  `mean_raw` and
+ * `std_raw` are the two linear layers' outputs, (N, T, A) contiguous on device,
+ * both EMB_F32 or both EMB_BF16 (the arithmetic is float32); `act` is (N, T, A)
+ * float32 or NULL (no action: logpi = 0).  Per element
+ *   EMB_NORMAL_BOUNDED  mean = tanh(m), std = (hi - lo) sigmoid(s + 2) + lo   (heads.py:150-152)
+ *   EMB_NORMAL_LOGSTD   mean = m,       std = exp(s)                           (heads.py:161)
+ *   z = (act - mean) / std
+ *   logp_a = -z^2 / 2 - log(std) - log(2 pi) / 2                              (outs.py:174-176)
+ *   ent_a  = log(2 pi std^2) / 2 + 1 / 2                                      (outs.py:178-179)
+ * and per output row r = (n, t), t < T - drop, summed over the A action dimensions
+ * in an order that A alone fixes (outs.py:63-64, 69-71):
+ *   logpi = sum_a logp_a,  ent = sum_a ent_a
+ *   loss  = weight[n * weight_stride + t] * -(logpi * adv[r] + actent * ent)
+ * `adv` (N, T - drop) and `weight` are float32 constants; either may be NULL: 1.
+ * `drop` is 0 or 1, the reference's [:, :-1]: a dropped step is not read.  One
+ * kernel launch each, no atomics, the same bits from run to run and whatever the
+ * alignment of the pointers:
+ *   emb_normal_policy_loss       loss, logpi, ent (N, T - drop) float32; each may be
+ *                                NULL (not written), not all three.
+ *   emb_normal_policy_loss_grad  grad_mean, grad_std (N, T, A) in the inputs' dtype =
+ *                                gout[r] * d loss[r] / d (m, s), the closed form
+ *                                  d / d m_a = -w g adv (z / std) dmean/dm
+ *                                  d / d s_a = -w g (adv (z^2 - 1) + actent) / std dstd/ds
+ *                                from one more read of the inputs; a dropped step's
+ *                                rows are written as zeros; T - drop may be 0.
+ *   emb_normal_sample            act[e] = mean_e + std_e * eps_e (outs.py:170-172),
+ *                                (rows, A) float32; eps (rows, A) float32 or, with eps
+ *                                NULL, the draw below at e = row * A + a.
+ *   emb_philox_normal            out[i] = eps(seed, offset, first + i), i < count: the
+ *                                Philox4x32-10 block keyed as emb_philox_uniform's,
+ *                                u1 = ((word 0 >> 8) + 1) * 2^-24 in (0, 1],
+ *                                u2 = (word 1 >> 8) * 2^-24,
+ *                                eps = sqrt(-2 ln u1) cos(2 pi u2).  It depends on
+ *                                (seed, offset, e) and on nothing else.
+ * `seed` and `offset` are passed by value: a captured graph replays the draw it
+ * captured; fresh noise inside a graph comes through `eps`.
+ * A NaN in m, s or act of a kept step makes that row's three outputs and its
+ * gradient rows NaN and touches no other row.  EMB_NORMAL_BOUNDED stays finite
+ * for m, s = +-1e4 (std is (hi - lo) * 0 + lo or (hi - lo) * 1 + lo, the gradient
+ * to m exactly 0); EMB_NORMAL_LOGSTD returns what the float32 arithmetic above
+ * returns when exp overflows (+-inf or NaN), confined to the row.
+ * EMB_ERR_INVALID before any launch: an unknown dtype or kind, N, T, rows or
+ * count < 0, drop outside {0, 1}, A outside 1 .. 256 (emb_normal_sample: A < 1),
+ * more than 2^31 - 1 elements, EMB_NORMAL_BOUNDED without finite hi >= lo > 0, a
+ * non-finite actent, weight_stride < T - drop, and with work to do a NULL input,
+ * gradient, act or out, or loss, logpi and ent all NULL.  No output rows:
+ * emb_normal_policy_loss launches nothing; emb_normal_policy_loss_grad still
+ * writes its zeros unless N * T = 0.                                            */
+#define EMB_NORMAL_BOUNDED 0
+#define EMB_NORMAL_LOGSTD 1
+int32_t emb_normal_policy_loss(const void* mean_raw, const void* std_raw, const void* act, int32_t dtype, int64_t N,
+                               int64_t T, int32_t drop, int64_t A, int32_t kind, float lo, float hi, float actent,
+                               const void* adv, const void* weight, int64_t weight_stride, void* loss, void* logpi,
+                               void* ent, void* stream);
+int32_t emb_normal_policy_loss_grad(const void* mean_raw, const void* std_raw, const void* act, int32_t dtype,
+                                    int64_t N, int64_t T, int32_t drop, int64_t A, int32_t kind, float lo, float hi,
+                                    float actent, const void* adv, const void* weight, int64_t weight_stride,
+                                    const void* gout, void* grad_mean, void* grad_std, void* stream);
+int32_t emb_normal_sample(const void* mean_raw, const void* std_raw, int32_t dtype, int64_t rows, int64_t A,
+                          int32_t kind, float lo, float hi, uint64_t seed, uint64_t offset, const void* eps, void* act,
+                          void* stream);
+int32_t emb_philox_normal(uint64_t seed, uint64_t offset, uint64_t first, int64_t count, void* out, void* stream);
+/* Kernel launches the four entry points above have issued in this process,
+ * counted where the kernels are launched.                                      */
+int32_t emb_normal_policy_launches(int64_t* count);
 
 /* ----------------------------------------------------------- collectives --
  * The two exchange steps of the sharded path on RCCL directly (xGMI inside one
