@@ -77,6 +77,19 @@ class NormalizeConfig(C.Structure):
       ('perclo', C.c_double), ('perchi', C.c_double)]
 
 
+class BlockLinearLaunch(C.Structure):
+  """emb_block_linear_launch_t: one launch of emb_block_linear_plan."""
+  _fields_ = [(name, C.c_int64) for name in (
+      'grid_x', 'grid_y', 'grid_z', 'block', 'passes', 'row_tile', 'col_tile', 'col_tiles', 'k_tile', 'k_steps')]
+
+
+class BlockLinearPlan(C.Structure):
+  """emb_block_linear_plan_t: what emb_block_linear_plan fills in."""
+  _fields_ = [('forward', BlockLinearLaunch), ('grad_x', BlockLinearLaunch), ('grad_w', BlockLinearLaunch)] + [
+      (name, C.c_int64) for name in (
+          'splits', 'split_rows', 'launches_grad_w', 'sum_grid_x', 'workspace_bytes', 'workspace_max_multiple')]
+
+
 class SelectorCallbacks(C.Structure):
   _fields_ = [
       ('user', C.c_void_p), ('sample', SAMPLE_FN), ('size', SIZE_FN),
@@ -225,6 +238,7 @@ SIGNATURES = {
     'emb_gru_gate': [p, p, i32, i64, i64, i64, p, p],
     'emb_gru_gate_grad': [p, p, p, i32, i64, i64, i64, p, p, p],
     'emb_gru_gate_launches': [p],
+    'emb_block_linear_plan': [i64, i64, i64, i64, i32, p],
     'emb_philox_uniform': [u64, u64, u64, i64, p, p],
     'emb_onehot_sample': [p, i32, i64, i64, i64, f32, i32, u64, u64, p, p, p, p],
     'emb_onehot_sample_grad': [p, p, i32, i64, i64, i64, f32, p, p],

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports (144 functions). */
+ * it exports (152 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -51,8 +51,8 @@ extern "C" {
  * emb_philox_uniform, emb_onehot_sample, emb_onehot_sample_grad,
  * emb_onehot_sample_launches, emb_recon_loss, emb_recon_loss_grad,
  * emb_recon_loss_launches, emb_normal_policy_loss, emb_normal_policy_loss_grad,
- * emb_normal_sample, emb_philox_normal, emb_normal_policy_launches (additions
- * only).                                                                       */
+ * emb_normal_sample, emb_philox_normal, emb_normal_policy_launches,
+ * emb_block_linear_plan (additions only).                                      */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -909,6 +909,46 @@ int32_t emb_gru_gate_grad(const void* x, const void* deter, const void* gout, in
 /* Kernel launches the two entry points above have issued in this process,
  * counted where the kernels are launched.                                      */
 int32_t emb_gru_gate_launches(int64_t* count);
+
+/* ---- BlockLinear, the RSSM's block-diagonal product: the launch plan
+ * `dynhid{i}` and `dyngru` of RSSM._core (dreamerv3/rssm.py:135-159) are
+ * BlockLinear layers (embodied/jax/nets.py:254-281): x (rows, g * I), kernel W
+ * (g, I, O), bias (g * O,),
+ *   out[r, k O + o]  = sum_i x[r, k I + i] W[k, i, o] + bias[k O + o]   (nets.py:269-277)
+ *   dx[r, k I + i]   = sum_o gout[r, k O + o] W[k, i, o]
+ *   dW[k, i, o]      = sum_r x[r, k I + i] gout[r, k O + o],  dbias[k O + o] = sum_r gout[r, k O + o].
+ * There are no kernels for it in this library yet; this is the host-side plan
+ * they are to be launched by, exported so that it can be held on a CPU first.
+ *   emb_block_linear_plan    the geometry of the three launches (forward, dx, dW +
+ *                            dbias) for a shape and a mask of the outputs wanted:
+ *                            grids, passes of the row loop, row splits of dW and
+ *                            the workspace bytes for their partial sums.  Needs
+ *                            no GPU and makes no HIP call.
+ * EMB_ERR_INVALID: plan NULL, outputs no mask of EMB_BLOCK_LINEAR_*, rows < 0, g,
+ * I or O below 1, g above 65535, I or O no multiple of 8 (16-byte rows of
+ * bfloat16), more than 2^31 - 1 elements of x, out or W, or, where dW or dbias is
+ * asked for, of workspace.  rows = 0: EMB_OK, all zeros.                       */
+#define EMB_BLOCK_LINEAR_OUT 1
+#define EMB_BLOCK_LINEAR_DX 2
+#define EMB_BLOCK_LINEAR_DW 4
+#define EMB_BLOCK_LINEAR_DBIAS 8
+typedef struct emb_block_linear_launch {
+  int64_t grid_x, grid_y, grid_z, block; /* all zero: not launched                    */
+  int64_t passes;                        /* trips of a workgroup's row loop            */
+  int64_t row_tile;                      /* rows a workgroup takes per trip            */
+  int64_t col_tile, col_tiles;           /* output columns per workgroup, and how many */
+  int64_t k_tile, k_steps;               /* of the other axis (summed, or I for dW)    */
+} emb_block_linear_launch_t;
+typedef struct emb_block_linear_plan {
+  emb_block_linear_launch_t forward, grad_x, grad_w; /* grad_w: grid_z = splits, rows summed */
+  int64_t splits, split_rows;  /* row splits of dW / dbias, rows of each (multiple of row_tile) */
+  int64_t launches_grad_w;     /* 1, or 2 with more than one split                     */
+  int64_t sum_grid_x;          /* the second launch's grid (block 256), 0 without      */
+  int64_t workspace_bytes;     /* partial sums of dW / dbias, 0 with one split         */
+  int64_t workspace_max_multiple; /* workspace_bytes <= this * bytes of dW, always     */
+} emb_block_linear_plan_t;
+int32_t emb_block_linear_plan(int64_t rows, int64_t g, int64_t I, int64_t O, int32_t outputs,
+                              emb_block_linear_plan_t* plan);
 
 /* ---- the draw of a one-hot latent or a discrete action, float32 arithmetic on device
  * DreamerV3 samples its stochastic state once per step of RSSM._observe and
