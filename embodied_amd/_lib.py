@@ -329,6 +329,14 @@ class _Api:
 api = _Api()
 
 
+def launches(name):
+  """Kernel launches the `name` family has issued in this process: what
+  `emb_<name>_launches` counts."""
+  count = C.c_int64(0)
+  getattr(api, f'emb_{name}_launches')(C.byref(count))
+  return count.value
+
+
 def _load_fastcall():
   """csrc/fastcall.c: the same exported functions called by address with cheap
   argument conversion (ctypes spends 1-2 us on a 10-12 argument call).  None if
@@ -440,6 +448,11 @@ def empty(shape, dtype, device):
 def ptr(array):
   """Address of a numpy array's buffer (None -> NULL)."""
   return None if array is None else array.ctypes.data
+
+
+def address(tensor):
+  """Address of a torch tensor's memory (None -> NULL)."""
+  return None if tensor is None else tensor.data_ptr()
 
 
 # Knobs that the Python layer reads (the rest belong to the C library): same

@@ -11,14 +11,13 @@ They feed what `outs` and `scans` consume: `_core`'s new `deter` goes through
 Inputs are torch CUDA tensors, float32 or bfloat16; the kernels' arithmetic is
 float32 and rounds once, at the store.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import api
+from ._lib import address as _address, api
+from .outs import _fused_path
 
 # What the kernels take: a row of at most 16 384 units stays in the registers of
 # one workgroup, indices are 32-bit.  Structural, not a crossover: the fused
@@ -41,16 +40,12 @@ _DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
 
 def norm_act_launches():
   """Kernel launches `emb_norm_act` and `emb_norm_act_grad` have issued in this process."""
-  count = C.c_int64(0)
-  api.emb_norm_act_launches(C.byref(count))
-  return count.value
+  return _lib.launches('norm_act')
 
 
 def gru_gate_launches():
   """Kernel launches `emb_gru_gate` and `emb_gru_gate_grad` have issued in this process."""
-  count = C.c_int64(0)
-  api.emb_gru_gate_launches(C.byref(count))
-  return count.value
+  return _lib.launches('gru_gate')
 
 
 def _norm_path(fused, rows, units):
@@ -58,32 +53,23 @@ def _norm_path(fused, rows, units):
   The kernels' median was below the composed path's at every shape, dtype and
   piece measured (profiles/rssm_core_bench.txt), so `fused=None` takes them
   wherever they fit: that held, no crossover constant."""
-  fits = 1 <= units <= NORM_ACT_MAX_UNITS and rows * units <= NORM_ACT_MAX_ELEMENTS
-  if fused and not 1 <= units <= NORM_ACT_MAX_UNITS:
-    raise ValueError(
-        f'norm_act(fused=True): {units} units, the kernels keep a row of at most {NORM_ACT_MAX_UNITS} in one '
-        'workgroup\'s registers (fused=None or False composes it)')
-  if fused and not fits:
-    raise ValueError(
-        f'norm_act(fused=True): {rows} x {units} elements, the kernels index at most 2^31 - 1 '
-        '(fused=None or False composes it)')
-  if fused is None:
-    return fits
-  return bool(fused)
+  row, index = 1 <= units <= NORM_ACT_MAX_UNITS, rows * units <= NORM_ACT_MAX_ELEMENTS
+  if row and index:
+    return fused is None or bool(fused)
+  return _fused_path(
+      'norm_act', fused,
+      (row, f'{units} units, the kernels keep a row of at most {NORM_ACT_MAX_UNITS} in one workgroup\'s registers'),
+      (index, f'{rows} x {units} elements, the kernels index at most 2^31 - 1'))
 
 
 def _gate_path(fused, rows, deter, blocks):
   """True: the kernel, False: the composed path (`gru_gate` says when).  As
   `_norm_path`: below the composed path at all 16 rows of profiles/rssm_core_bench.txt,
   so wherever it fits."""
-  fits = rows * 3 * deter <= GRU_GATE_MAX_ELEMENTS
-  if fused and not fits:
-    raise ValueError(
-        f'gru_gate(fused=True): {rows} x {3 * deter} elements of x, the kernels index at most 2^31 - 1 '
-        '(fused=None or False composes it)')
-  if fused is None:
-    return fits
-  return bool(fused)
+  if rows * 3 * deter <= GRU_GATE_MAX_ELEMENTS:
+    return fused is None or bool(fused)
+  return _fused_path(
+      'gru_gate', fused, (False, f'{rows} x {3 * deter} elements of x, the kernels index at most 2^31 - 1'))
 
 
 def _check_device(who, x):
@@ -151,10 +137,9 @@ class _FusedNormAct(torch.autograd.Function):
     units = x.shape[-1]
     flat = x.detach().reshape(-1, units).contiguous()
     out = torch.empty_like(flat)
-    address = lambda tensor: None if tensor is None else tensor.data_ptr()
     scale = None if scale is None else scale.detach().contiguous()
     shift = None if shift is None else shift.detach().contiguous()
-    api.emb_norm_act(flat.data_ptr(), address(scale), address(shift), _DTYPES[x.dtype], flat.shape[0], units, impl,
+    api.emb_norm_act(flat.data_ptr(), _address(scale), _address(shift), _DTYPES[x.dtype], flat.shape[0], units, impl,
                      act, eps, out.data_ptr(), _lib.raw_stream(x.device))
     ctx.saved = (flat, scale, shift, impl, act, eps, x.shape)
     ctx.set_materialize_grads(False)
@@ -179,10 +164,9 @@ class _FusedNormAct(torch.autograd.Function):
       partials = _lib.empty((floats,), torch.float32, flat.device)
     if dx is None and dscale is None and dshift is None:
       return (None,) * 6
-    address = lambda tensor: None if tensor is None else tensor.data_ptr()
     api.emb_norm_act_grad(
-        flat.data_ptr(), address(scale), address(shift), gout.data_ptr(), _DTYPES[flat.dtype], rows, units, impl, act,
-        eps, address(dx), address(dscale), address(dshift), address(partials), floats, _lib.raw_stream(flat.device))
+        flat.data_ptr(), _address(scale), _address(shift), gout.data_ptr(), _DTYPES[flat.dtype], rows, units, impl, act,
+        eps, _address(dx), _address(dscale), _address(dshift), _address(partials), floats, _lib.raw_stream(flat.device))
     if ctx.needs_input_grad[2] and dshift is None:      # rms does not read its shift
       dshift = torch.zeros_like(shift)
     return (None if dx is None else dx.view(shape), dscale, dshift, None, None, None)
@@ -319,9 +303,8 @@ class _FusedGate(torch.autograd.Function):
     gout = gout.to(ds.dtype).reshape(ds.shape).contiguous()
     dx = torch.empty_like(xs) if want_x else None
     ddeter = torch.empty_like(ds) if want_deter else None
-    address = lambda tensor: None if tensor is None else tensor.data_ptr()
     api.emb_gru_gate_grad(xs.data_ptr(), ds.data_ptr(), gout.data_ptr(), _DTYPES[ds.dtype], ds.shape[0], ds.shape[1],
-                          blocks, address(dx), address(ddeter), _lib.raw_stream(ds.device))
+                          blocks, _address(dx), _address(ddeter), _lib.raw_stream(ds.device))
     return (None if dx is None else dx.view(xshape), None if ddeter is None else ddeter.view(dshape), None)
 
 

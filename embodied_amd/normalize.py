@@ -22,9 +22,7 @@ _WORDS = {'meanstd': ('mean', 'sqrs'), 'perc': ('lo', 'hi')}
 
 def launches():
   """Kernel launches `emb_normalize` has issued in this process."""
-  count = C.c_int64(0)
-  _lib.api.emb_normalize_launches(C.byref(count))
-  return count.value
+  return _lib.launches('normalize')
 
 
 class DeviceNormalize:

@@ -60,9 +60,7 @@ _GRADS = {torch.float32: 0, torch.bfloat16: BF16}
 def optimizer_launches():
   """Kernel launches `emb_optim_norms`, `emb_optim_update` and `emb_optim_metrics`
   have issued in this process."""
-  count = C.c_int64(0)
-  api.emb_optim_launches(C.byref(count))
-  return count.value
+  return _lib.launches('optim')
 
 
 def warmup_schedule(lr, warmup):

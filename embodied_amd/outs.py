@@ -23,7 +23,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import api
+from ._lib import address as _address, api
 
 # What the kernels take: a row of at most 1024 bins stays in one wave's
 # registers, indices are 32-bit.  Structural, not a crossover: the fused median
@@ -60,9 +60,42 @@ def symexp_twohot_bins(n=255):
 def twohot_launches():
   """Kernel launches `emb_twohot_stats`, `emb_twohot_loss` and `emb_twohot_grad`
   have issued in this process."""
-  count = C.c_int64(0)
-  api.emb_twohot_launches(C.byref(count))
-  return count.value
+  return _lib.launches('twohot')
+
+
+def _check_device(logits):
+  if not (torch.is_tensor(logits) and logits.is_cuda):
+    raise RuntimeError('embodied_amd.outs runs as HIP kernels: pass CUDA tensors (no CPU fallback)')
+
+
+def _cuda_device(device):
+  """`device` (None: the current CUDA device) as a torch.device, which must be a CUDA one."""
+  device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+  if device.type != 'cuda':
+    raise RuntimeError('embodied_amd.outs runs as HIP kernels: pass a CUDA device (no CPU fallback)')
+  return device
+
+
+def _fused_path(head, fused, *limits):
+  """The decision every head and net makes between its two paths.  True: the
+  kernels, False: the composed path.  `limits` is what the kernels take, in the
+  order it is checked, as (holds, wording).  `fused=None` takes the kernels
+  wherever every limit holds -- each family's kernels were below its composed
+  path at every shape measured; the figures stand beside its `*_MAX_*` constants
+  or its `_xxx_path` -- and any other value forces a path by its truth; forcing
+  the kernels past a limit raises the wording of the first that fails.
+
+  Where everything holds -- every call of a training step -- the `_xxx_path`
+  functions answer `fused is None or bool(fused)` themselves and do not come
+  here: a decision is part of the host's enqueue, which is all a small fused
+  call costs, and the wordings are only worth making for a refusal."""
+  fits = True
+  for holds, wording in limits:
+    if not holds:
+      if fused:
+        raise ValueError(f'{head}(fused=True): {wording} (fused=None or False composes it)')
+      fits = False
+  return fits if fused is None else bool(fused)
 
 
 def _host_bins(bins, n):
@@ -100,18 +133,13 @@ def _path(fused, n, rows):
   """True: the kernels, False: the composed path (`TwoHot` says when).  The
   kernels' median was below the composed path's at every shape and piece measured
   (profiles/twohot_bench.txt), so `fused=None` takes them wherever they fit."""
-  fits = n <= TWOHOT_MAX_BINS and rows * n <= TWOHOT_MAX_LOGITS
-  if fused and n > TWOHOT_MAX_BINS:
-    raise ValueError(
-        f'TwoHot(fused=True): {n} bins, the kernels keep a row of at most {TWOHOT_MAX_BINS} in one wave\'s '
-        'registers (fused=None or False composes it)')
-  if fused and not fits:
-    raise ValueError(
-        f'TwoHot(fused=True): {rows} x {n} logits, the kernels index at most 2^31 - 1 '
-        '(fused=None or False composes it)')
-  if fused is None:
-    return fits
-  return bool(fused)
+  row, index = n <= TWOHOT_MAX_BINS, rows * n <= TWOHOT_MAX_LOGITS
+  if row and index:
+    return fused is None or bool(fused)
+  return _fused_path(
+      'TwoHot', fused,
+      (row, f'{n} bins, the kernels keep a row of at most {TWOHOT_MAX_BINS} in one wave\'s registers'),
+      (index, f'{rows} x {n} logits, the kernels index at most 2^31 - 1'))
 
 
 def _check_sum(targets, coefs):
@@ -210,8 +238,7 @@ class TwoHot:
   def __init__(self, logits, bins, fused=None):
     n = logits.shape[-1] if torch.is_tensor(logits) and logits.dim() else np.shape(logits)[-1]
     host = _host_bins(bins, n)
-    if not (torch.is_tensor(logits) and logits.is_cuda):
-      raise RuntimeError('embodied_amd.outs runs as HIP kernels: pass CUDA tensors (no CPU fallback)')
+    _check_device(logits)
     if logits.dtype not in _DTYPES:
       raise TypeError(f'TwoHot: logits must be float32 or bfloat16, got {logits.dtype}')
     self.logits = logits
@@ -315,9 +342,7 @@ ONEHOT_MAX_LOGITS = 2 ** 31 - 1
 def onehot_kl_launches():
   """Kernel launches `emb_onehot_kl` and `emb_onehot_kl_grad` have issued in
   this process."""
-  count = C.c_int64(0)
-  api.emb_onehot_kl_launches(C.byref(count))
-  return count.value
+  return _lib.launches('onehot_kl')
 
 
 def _kl_path(fused, rows, stoch, classes):
@@ -325,18 +350,14 @@ def _kl_path(fused, rows, stoch, classes):
   The kernels' median was below the composed path's at every shape, dtype and
   piece measured (profiles/rssm_kl_bench.txt), so `fused=None` takes them
   wherever they fit."""
-  fits = 1 <= classes <= ONEHOT_MAX_CLASSES and stoch >= 1 and rows * stoch * classes <= ONEHOT_MAX_LOGITS
-  if fused and not 1 <= classes <= ONEHOT_MAX_CLASSES:
-    raise ValueError(
-        f'OneHot(fused=True): {classes} classes, the kernels keep a group of at most {ONEHOT_MAX_CLASSES} in one '
-        'wave\'s registers (fused=None or False composes it)')
-  if fused and not fits:
-    raise ValueError(
-        f'OneHot(fused=True): {rows} x {stoch} x {classes} logits, the kernels index 1 .. 2^31 - 1 '
-        '(fused=None or False composes it)')
-  if fused is None:
-    return fits
-  return bool(fused)
+  group = 1 <= classes <= ONEHOT_MAX_CLASSES
+  index = stoch >= 1 and rows * stoch * classes <= ONEHOT_MAX_LOGITS
+  if group and index:
+    return fused is None or bool(fused)
+  return _fused_path(
+      'OneHot', fused,
+      (group, f'{classes} classes, the kernels keep a group of at most {ONEHOT_MAX_CLASSES} in one wave\'s registers'),
+      (index, f'{rows} x {stoch} x {classes} logits, the kernels index 1 .. 2^31 - 1'))
 
 
 def _onehot_logits(logits, unimix):
@@ -386,10 +407,9 @@ def _kl_backward(x, y, dtype, unimix, free_nats, kl, g_rep, g_dyn, lead):
     return None, None
   grad_post = None if g_rep is None else torch.empty_like(x)
   grad_prior = None if g_dyn is None else torch.empty_like(y)
-  address = lambda t: None if t is None else t.data_ptr()
   api.emb_onehot_kl_grad(
-      x.data_ptr(), y.data_ptr(), dtype, rows, stoch, classes, unimix, free_nats, kl.data_ptr(), address(g_rep),
-      address(g_dyn), address(grad_post), address(grad_prior), _lib.raw_stream(x.device))
+      x.data_ptr(), y.data_ptr(), dtype, rows, stoch, classes, unimix, free_nats, kl.data_ptr(), _address(g_rep),
+      _address(g_dyn), _address(grad_post), _address(grad_prior), _lib.raw_stream(x.device))
   return grad_post, grad_prior
 
 
@@ -443,8 +463,7 @@ class _FusedKL(torch.autograd.Function):
 
 
 def _check_onehot(who, logits):
-  if not (torch.is_tensor(logits) and logits.is_cuda):
-    raise RuntimeError('embodied_amd.outs runs as HIP kernels: pass CUDA tensors (no CPU fallback)')
+  _check_device(logits)
   if logits.dtype not in _DTYPES:
     raise TypeError(f'{who}: logits must be float32 or bfloat16, got {logits.dtype}')
   if logits.dim() < 2:
@@ -488,9 +507,7 @@ _SAMPLE_DRAW, _SAMPLE_PRED = 0, 1
 def onehot_sample_launches():
   """Kernel launches `emb_philox_uniform`, `emb_onehot_sample` and
   `emb_onehot_sample_grad` have issued in this process."""
-  count = C.c_int64(0)
-  api.emb_onehot_sample_launches(C.byref(count))
-  return count.value
+  return _lib.launches('onehot_sample')
 
 
 def _check_counter(who, name, value):
@@ -502,25 +519,28 @@ def _check_counter(who, name, value):
   return value
 
 
+def _philox(entry, who, what, seed, offset, first, count, device):
+  """`philox_uniform` and `philox_normal`: `entry` is the entry point that fills
+  the result, `who` the function's name in the refusals, `what` what it counts."""
+  seed = _check_counter(who, 'seed', seed)
+  offset = _check_counter(who, 'offset', offset)
+  first = _check_counter(who, 'first', first)
+  count = int(count)
+  if count < 0 or first + count > 2 ** 64:
+    raise ValueError(f'{who}: count = {count} from first = {first}, needs 0 <= count and {what} below 2^64')
+  out = torch.empty((count,), dtype=torch.float32, device=_cuda_device(device))
+  if count:
+    entry(seed, offset, first, count, out.data_ptr(), _lib.raw_stream(out.device))
+  return out
+
+
 def philox_uniform(seed, offset=0, first=0, count=1, device=None):
   """(count,) float32 on `device`: the uniforms the sample kernels draw for the
   groups `first .. first + count - 1` -- Philox4x32-10 with key
   (seed & 0xffffffff, seed >> 32) and counter (g & 0xffffffff, g >> 32,
   offset & 0xffffffff, offset >> 32), u = (word 0 >> 8) * 2^-24 in [0, 1).  One
   launch (`emb_philox_uniform`); count = 0 launches nothing."""
-  seed = _check_counter('philox_uniform', 'seed', seed)
-  offset = _check_counter('philox_uniform', 'offset', offset)
-  first = _check_counter('philox_uniform', 'first', first)
-  count = int(count)
-  if count < 0 or first + count > 2 ** 64:
-    raise ValueError(f'philox_uniform: count = {count} from first = {first}, needs 0 <= count and groups below 2^64')
-  device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-  if device.type != 'cuda':
-    raise RuntimeError('embodied_amd.outs runs as HIP kernels: pass a CUDA device (no CPU fallback)')
-  out = torch.empty((count,), dtype=torch.float32, device=device)
-  if count:
-    api.emb_philox_uniform(seed, offset, first, count, out.data_ptr(), _lib.raw_stream(out.device))
-  return out
+  return _philox(api.emb_philox_uniform, 'philox_uniform', 'groups', seed, offset, first, count, device)
 
 
 def _sample_path(who, fused, rows, groups, classes):
@@ -532,18 +552,14 @@ def _sample_path(who, fused, rows, groups, classes):
   328.4; (16384, 32, 64) bf16: 238.5 / 3619.9 and 465.0 / 4162.9 -- so `fused=None`
   takes them wherever they fit.  Up to 1024 rows the fused forward is the host's
   enqueue, about 17 us whatever the size (the entry point alone: 4 .. 18 us)."""
-  fits = 1 <= classes <= SAMPLE_MAX_CLASSES and groups >= 1 and rows * groups * classes <= SAMPLE_MAX_LOGITS
-  if fused and not 1 <= classes <= SAMPLE_MAX_CLASSES:
-    raise ValueError(
-        f'{who}(fused=True): {classes} classes, the kernels keep a group of at most {SAMPLE_MAX_CLASSES} in one '
-        'wave\'s registers (fused=None or False composes it)')
-  if fused and not fits:
-    raise ValueError(
-        f'{who}(fused=True): {rows} x {groups} x {classes} logits, the kernels index 1 .. 2^31 - 1 '
-        '(fused=None or False composes it)')
-  if fused is None:
-    return fits
-  return bool(fused)
+  group = 1 <= classes <= SAMPLE_MAX_CLASSES
+  index = groups >= 1 and rows * groups * classes <= SAMPLE_MAX_LOGITS
+  if group and index:
+    return fused is None or bool(fused)
+  return _fused_path(
+      who, fused,
+      (group, f'{classes} classes, the kernels keep a group of at most {SAMPLE_MAX_CLASSES} in one wave\'s registers'),
+      (index, f'{rows} x {groups} x {classes} logits, the kernels index 1 .. 2^31 - 1'))
 
 
 def _sample_args(who, logits, seed, offset, uniform):
@@ -566,10 +582,9 @@ def _fused_sample(x, rows, groups, unimix, mode, seed, offset, uniform, want_ind
   """One launch: (index int32 (rows * groups,) or None, onehot like x or None)."""
   index = _lib.empty((rows * groups,), torch.int32, x.device) if want_index else None
   onehot = torch.empty_like(x) if want_onehot else None
-  address = lambda t: None if t is None else t.data_ptr()
   api.emb_onehot_sample(
-      x.data_ptr(), _DTYPES[x.dtype], rows, groups, x.shape[-1], unimix, mode, seed, offset, address(uniform),
-      address(index), address(onehot), _lib.raw_stream(x.device))
+      x.data_ptr(), _DTYPES[x.dtype], rows, groups, x.shape[-1], unimix, mode, seed, offset, _address(uniform),
+      _address(index), _address(onehot), _lib.raw_stream(x.device))
   return index, onehot
 
 
@@ -815,9 +830,7 @@ POLICY_MAX_LOGITS = 2 ** 31 - 1
 def policy_loss_launches():
   """Kernel launches `emb_policy_loss` and `emb_policy_loss_grad` have issued in
   this process."""
-  count = C.c_int64(0)
-  api.emb_policy_loss_launches(C.byref(count))
-  return count.value
+  return _lib.launches('policy_loss')
 
 
 def _policy_path(fused, rows, groups, classes):
@@ -825,23 +838,14 @@ def _policy_path(fused, rows, groups, classes):
   `rows` counts the logits' rows, a dropped step's included.  The kernels' median
   was below the composed path's at every shape, dtype and piece measured
   (profiles/policy_loss_bench.txt), so `fused=None` takes them wherever they fit."""
-  fits = 1 <= classes <= POLICY_MAX_CLASSES and groups >= 1 and rows * groups * classes <= POLICY_MAX_LOGITS
-  if fused and not 1 <= classes <= POLICY_MAX_CLASSES:
-    raise ValueError(
-        f'Categorical(fused=True): {classes} classes, the kernels keep a group of at most {POLICY_MAX_CLASSES} in '
-        'one wave\'s registers (fused=None or False composes it)')
-  if fused and not fits:
-    raise ValueError(
-        f'Categorical(fused=True): {rows} x {groups} x {classes} logits, the kernels index 1 .. 2^31 - 1 '
-        '(fused=None or False composes it)')
-  if fused is None:
-    return fits
-  return bool(fused)
-
-
-def _check_device(logits):
-  if not (torch.is_tensor(logits) and logits.is_cuda):
-    raise RuntimeError('embodied_amd.outs runs as HIP kernels: pass CUDA tensors (no CPU fallback)')
+  group = 1 <= classes <= POLICY_MAX_CLASSES
+  index = groups >= 1 and rows * groups * classes <= POLICY_MAX_LOGITS
+  if group and index:
+    return fused is None or bool(fused)
+  return _fused_path(
+      'Categorical', fused,
+      (group, f'{classes} classes, the kernels keep a group of at most {POLICY_MAX_CLASSES} in one wave\'s registers'),
+      (index, f'{rows} x {groups} x {classes} logits, the kernels index 1 .. 2^31 - 1'))
 
 
 def _check_categorical(who, logits, dims):
@@ -903,10 +907,9 @@ class _FusedPolicy(torch.autograd.Function):
     x = logits.detach().contiguous()
     dtype = _DTYPES[logits.dtype]
     loss, logpi, ent = _lib.empty((3, n * (t - drop)), torch.float32, x.device).unbind(0)
-    address = lambda tensor: None if tensor is None else tensor.data_ptr()
     api.emb_policy_loss(
-        x.data_ptr(), address(act), dtype, n, t, drop, groups, classes, unimix, actent, address(adv), address(weight),
-        stride, loss.data_ptr(), logpi.data_ptr(), ent.data_ptr(), _lib.raw_stream(x.device))
+        x.data_ptr(), _address(act), dtype, n, t, drop, groups, classes, unimix, actent, _address(adv),
+        _address(weight), stride, loss.data_ptr(), logpi.data_ptr(), ent.data_ptr(), _lib.raw_stream(x.device))
     ctx.saved = (x, act, adv, weight, stride, geometry, unimix, actent, dtype, logits.shape)
     ctx.set_materialize_grads(False)
     ctx.mark_non_differentiable(logpi, ent)
@@ -921,10 +924,9 @@ class _FusedPolicy(torch.autograd.Function):
     n, t, drop, groups, classes = geometry
     gout = gout.to(torch.float32).contiguous()
     grad = torch.empty_like(x)
-    address = lambda tensor: None if tensor is None else tensor.data_ptr()
     api.emb_policy_loss_grad(
-        x.data_ptr(), address(act), dtype, n, t, drop, groups, classes, unimix, actent, address(adv), address(weight),
-        stride, gout.data_ptr(), grad.data_ptr(), _lib.raw_stream(x.device))
+        x.data_ptr(), _address(act), dtype, n, t, drop, groups, classes, unimix, actent, _address(adv),
+        _address(weight), stride, gout.data_ptr(), grad.data_ptr(), _lib.raw_stream(x.device))
     return (grad.view(shape),) + (None,) * 7
 
 
@@ -1006,6 +1008,47 @@ class Categorical:
     return _composed_cat_entropy(_onehot_logits(self.logits, self.unimix), self.dims)
 
 
+# The frame of the actor's loss (agent.py:411-415), what `policy_loss` and
+# `normal_policy_loss` share: `who` is the caller's name in the refusals.
+
+def _loss_frame(who, what, x, lead, actent, drop_last):
+  """(actent, n, t, drop, kept, out_shape) of a loss over the leading shape `lead`
+  of `x`, the `what` of the time-axis refusal: n sequences of t steps, of which
+  the first `kept` make the outputs."""
+  actent = float(actent)
+  if not np.isfinite(actent):
+    raise ValueError(f'{who}: actent = {actent}, needs a finite value')
+  drop = 1 if drop_last else 0
+  if drop and not lead:
+    raise ValueError(f'{who}: drop_last needs a time axis, {what} of shape {tuple(x.shape)}')
+  n, t = (int(np.prod(lead[:-1], dtype=np.int64)), lead[-1]) if drop else (int(np.prod(lead, dtype=np.int64)), 1)
+  kept = max(t - drop, 0)
+  return actent, n, t, drop, kept, (*lead[:-1], kept) if drop else tuple(lead)
+
+
+def _loss_constant(who, name, value, shapes, device):
+  """`adv` or `weight`: float32 and contiguous on `device`, in one of `shapes`; a constant."""
+  if not torch.is_tensor(value):
+    value = torch.as_tensor(np.asarray(value, np.float32))
+  if tuple(value.shape) not in shapes:
+    raise ValueError(f'{who}: {name} of shape {tuple(value.shape)}, needs ' +
+                     ' or '.join(str(tuple(s)) for s in shapes))
+  return value.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def _kept_steps(lead, drop, kept, weight, *tensors):
+  """The reference's [:, :-1], taken before the arithmetic instead of after: a dropped step takes no part."""
+  if not drop:
+    return (weight, *tensors)
+  axis = len(lead) - 1
+  return (weight[..., :kept], *(x.narrow(axis, 0, kept) for x in tensors))
+
+
+def _composed_loss(logpi, ent, adv, weight, actent):
+  loss = weight * -(logpi * adv + actent * ent)
+  return {'loss': loss, 'logpi': logpi.detach(), 'ent': ent.detach()}
+
+
 def policy_loss(logits, act, adv, weight, actent=3e-4, unimix=0.0, dims=0, drop_last=True, fused=None):
   """The actor's loss of `imag_loss` (agent.py:411-415) for one action key:
 
@@ -1054,41 +1097,19 @@ def policy_loss(logits, act, adv, weight, actent=3e-4, unimix=0.0, dims=0, drop_
   row's three outputs."""
   _check_categorical('policy_loss', logits, dims)
   unimix = _check_unimix('policy_loss', unimix)
-  actent = float(actent)
-  if not np.isfinite(actent):
-    raise ValueError(f'policy_loss: actent = {actent}, needs a finite value')
   lead = logits.shape[:-1 - dims]
   groups, classes = (logits.shape[-2] if dims else 1), logits.shape[-1]
-  drop = 1 if drop_last else 0
-  if drop and not lead:
-    raise ValueError(f'policy_loss: drop_last needs a time axis, logits of shape {tuple(logits.shape)}')
-  n, t = (int(np.prod(lead[:-1], dtype=np.int64)), lead[-1]) if drop else (int(np.prod(lead, dtype=np.int64)), 1)
-  kept = max(t - drop, 0)
-  out_shape = (*lead[:-1], kept) if drop else tuple(lead)
+  actent, n, t, drop, kept, out_shape = _loss_frame('policy_loss', 'logits', logits, lead, actent, drop_last)
   act = _actions('policy_loss', act, logits, dims)
-
-  def constant(name, value, shapes):
-    if not torch.is_tensor(value):
-      value = torch.as_tensor(np.asarray(value, np.float32))
-    if tuple(value.shape) not in shapes:
-      raise ValueError(f'policy_loss: {name} of shape {tuple(value.shape)}, needs ' +
-                       ' or '.join(str(tuple(s)) for s in shapes))
-    return value.detach().to(device=logits.device, dtype=torch.float32).contiguous()
-
-  adv = constant('adv', adv, (out_shape,))
-  weight = constant('weight', weight, (out_shape, tuple(lead)))
+  adv = _loss_constant('policy_loss', 'adv', adv, (out_shape,), logits.device)
+  weight = _loss_constant('policy_loss', 'weight', weight, (out_shape, tuple(lead)), logits.device)
   if _policy_path(fused, n * t, groups, classes) and n * kept > 0 and groups > 0:
-    stride = weight.shape[-1] if drop else 1
-    loss, logpi, ent = _FusedPolicy.apply(logits, act, adv, weight, stride, (n, t, drop, groups, classes), unimix, actent)
+    stride, geometry = weight.shape[-1] if drop else 1, (n, t, drop, groups, classes)
+    loss, logpi, ent = _FusedPolicy.apply(logits, act, adv, weight, stride, geometry, unimix, actent)
     return {'loss': loss.view(out_shape), 'logpi': logpi.view(out_shape), 'ent': ent.view(out_shape)}
-  if drop:      # the reference's [:, :-1], taken before the arithmetic instead of after: a dropped step takes no part
-    axis = len(lead) - 1
-    logits, act, weight = logits.narrow(axis, 0, kept), act.narrow(axis, 0, kept), weight[..., :kept]
+  weight, logits, act = _kept_steps(lead, drop, kept, weight, logits, act)
   dist = _onehot_logits(logits, unimix)
-  logpi = _composed_logp(dist, act, dims)
-  ent = _composed_cat_entropy(dist, dims)
-  loss = weight * -(logpi * adv + actent * ent)
-  return {'loss': loss, 'logpi': logpi.detach(), 'ent': ent.detach()}
+  return _composed_loss(_composed_logp(dist, act, dims), _composed_cat_entropy(dist, dims), adv, weight, actent)
 
 
 # ---- the reconstruction heads: image MSE from uint8, symlog MSE, Binary ----------
@@ -1102,9 +1123,7 @@ _RECON_TARGETS = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.uint
 def recon_loss_launches():
   """Kernel launches `emb_recon_loss` and `emb_recon_loss_grad` have issued in
   this process."""
-  count = C.c_int64(0)
-  api.emb_recon_loss_launches(C.byref(count))
-  return count.value
+  return _lib.launches('recon_loss')
 
 
 def _recon_path(who, fused, rows, units):
@@ -1118,14 +1137,9 @@ def _recon_path(who, fused, rows, units):
   (1024, 1024): 16.6 / 37.3 and 70.5 / 94.2 -- so `fused=None` takes them wherever
   they fit and no size constant sits here.  Below about a megabyte the fused
   forward is the host's enqueue, about 16.5 us whatever the size."""
-  fits = units >= 1 and rows * units <= RECON_MAX_ELEMENTS
-  if fused and not fits:
-    raise ValueError(
-        f'{who}(fused=True): {rows} x {units} elements, the kernels index 1 .. 2^31 - 1 '
-        '(fused=None or False composes it)')
-  if fused is None:
-    return fits
-  return bool(fused)
+  if units >= 1 and rows * units <= RECON_MAX_ELEMENTS:
+    return fused is None or bool(fused)
+  return _fused_path(who, fused, (False, f'{rows} x {units} elements, the kernels index 1 .. 2^31 - 1'))
 
 
 def _recon_geometry(who, x, dims):
@@ -1357,9 +1371,7 @@ _TWO_PI = float(np.float32(2 * np.pi))
 def normal_policy_launches():
   """Kernel launches `emb_normal_policy_loss`, `emb_normal_policy_loss_grad`,
   `emb_normal_sample` and `emb_philox_normal` have issued in this process."""
-  count = C.c_int64(0)
-  api.emb_normal_policy_launches(C.byref(count))
-  return count.value
+  return _lib.launches('normal_policy')
 
 
 def philox_normal(seed, offset=0, first=0, count=1, device=None):
@@ -1368,19 +1380,7 @@ def philox_normal(seed, offset=0, first=0, count=1, device=None):
   `philox_uniform`'s, u1 = ((word 0 >> 8) + 1) * 2^-24 in (0, 1], u2 = (word 1 >> 8) *
   2^-24, eps = sqrt(-2 ln u1) cos(2 pi u2).  One launch (`emb_philox_normal`);
   count = 0 launches nothing."""
-  seed = _check_counter('philox_normal', 'seed', seed)
-  offset = _check_counter('philox_normal', 'offset', offset)
-  first = _check_counter('philox_normal', 'first', first)
-  count = int(count)
-  if count < 0 or first + count > 2 ** 64:
-    raise ValueError(f'philox_normal: count = {count} from first = {first}, needs 0 <= count and elements below 2^64')
-  device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-  if device.type != 'cuda':
-    raise RuntimeError('embodied_amd.outs runs as HIP kernels: pass a CUDA device (no CPU fallback)')
-  out = torch.empty((count,), dtype=torch.float32, device=device)
-  if count:
-    api.emb_philox_normal(seed, offset, first, count, out.data_ptr(), _lib.raw_stream(out.device))
-  return out
+  return _philox(api.emb_philox_normal, 'philox_normal', 'elements', seed, offset, first, count, device)
 
 
 def _normal_path(fused, rows, actions):
@@ -1393,18 +1393,14 @@ def _normal_path(fused, rows, actions):
   43.2 -- so `fused=None` takes them wherever they fit.  Up to (16384, 16, 6) the
   fused figures are the host's enqueue (23 us forward, 95 with autograd's
   backward, 12.5 for the sample) whatever the size."""
-  fits = 1 <= actions <= NORMAL_MAX_ACTIONS and rows * actions <= NORMAL_MAX_ELEMENTS
-  if fused and not 1 <= actions <= NORMAL_MAX_ACTIONS:
-    raise ValueError(
-        f'Normal(fused=True): {actions} action dimensions, the kernels keep a row of at most {NORMAL_MAX_ACTIONS} in '
-        'one wave\'s registers (fused=None or False composes it)')
-  if fused and not fits:
-    raise ValueError(
-        f'Normal(fused=True): {rows} x {actions} elements, the kernels index 1 .. 2^31 - 1 '
-        '(fused=None or False composes it)')
-  if fused is None:
-    return fits
-  return bool(fused)
+  row, index = 1 <= actions <= NORMAL_MAX_ACTIONS, rows * actions <= NORMAL_MAX_ELEMENTS
+  if row and index:
+    return fused is None or bool(fused)
+  return _fused_path(
+      'Normal', fused,
+      (row, f'{actions} action dimensions, the kernels keep a row of at most {NORMAL_MAX_ACTIONS} in one wave\'s '
+            'registers'),
+      (index, f'{rows} x {actions} elements, the kernels index 1 .. 2^31 - 1'))
 
 
 def _check_normal(who, mean_raw, std_raw, kind, minstd, maxstd, dims):
@@ -1475,10 +1471,9 @@ class _FusedNormalPolicy(torch.autograd.Function):
     m, s = mean_raw.detach().contiguous(), std_raw.detach().contiguous()
     dtype = _DTYPES[m.dtype]
     loss, logpi, ent = _lib.empty((3, n * (t - drop)), torch.float32, m.device).unbind(0)
-    address = lambda tensor: None if tensor is None else tensor.data_ptr()
     api.emb_normal_policy_loss(
-        m.data_ptr(), s.data_ptr(), address(act), dtype, n, t, drop, actions, *head, actent, address(adv),
-        address(weight), stride, loss.data_ptr(), logpi.data_ptr(), ent.data_ptr(), _lib.raw_stream(m.device))
+        m.data_ptr(), s.data_ptr(), _address(act), dtype, n, t, drop, actions, *head, actent, _address(adv),
+        _address(weight), stride, loss.data_ptr(), logpi.data_ptr(), ent.data_ptr(), _lib.raw_stream(m.device))
     ctx.saved = (m, s, act, adv, weight, stride, geometry, head, actent, dtype, mean_raw.shape)
     ctx.set_materialize_grads(False)
     ctx.mark_non_differentiable(logpi, ent)
@@ -1493,10 +1488,9 @@ class _FusedNormalPolicy(torch.autograd.Function):
     n, t, drop, actions = geometry
     gout = gout.to(torch.float32).contiguous()
     grad_mean, grad_std = torch.empty_like(m), torch.empty_like(s)
-    address = lambda tensor: None if tensor is None else tensor.data_ptr()
     api.emb_normal_policy_loss_grad(
-        m.data_ptr(), s.data_ptr(), address(act), dtype, n, t, drop, actions, *head, actent, address(adv),
-        address(weight), stride, gout.data_ptr(), grad_mean.data_ptr(), grad_std.data_ptr(), _lib.raw_stream(m.device))
+        m.data_ptr(), s.data_ptr(), _address(act), dtype, n, t, drop, actions, *head, actent, _address(adv),
+        _address(weight), stride, gout.data_ptr(), grad_mean.data_ptr(), grad_std.data_ptr(), _lib.raw_stream(m.device))
     return (grad_mean.view(shape), grad_std.view(shape)) + (None,) * 7
 
 
@@ -1649,41 +1643,19 @@ def normal_policy_loss(mean_raw, std_raw, act, adv, weight, actent=3e-4, kind='b
   values of +-1e4: the stddev is the formula's value at sigmoid = 0 or 1 and the
   gradient to `mean_raw` is exactly 0 on the kernels.  'logstd' returns what the
   float32 definition returns when `exp` overflows (+-inf or NaN), confined to the row."""
-  head = _check_normal('normal_policy_loss', mean_raw, std_raw, kind, minstd, maxstd, dims)
-  actent = float(actent)
-  if not np.isfinite(actent):
-    raise ValueError(f'normal_policy_loss: actent = {actent}, needs a finite value')
+  who = 'normal_policy_loss'
+  head = _check_normal(who, mean_raw, std_raw, kind, minstd, maxstd, dims)
   lead = mean_raw.shape[:mean_raw.dim() - dims]
   actions = mean_raw.shape[-1] if dims else 1
-  drop = 1 if drop_last else 0
-  if drop and not lead:
-    raise ValueError(f'normal_policy_loss: drop_last needs a time axis, inputs of shape {tuple(mean_raw.shape)}')
-  n, t = (int(np.prod(lead[:-1], dtype=np.int64)), lead[-1]) if drop else (int(np.prod(lead, dtype=np.int64)), 1)
-  kept = max(t - drop, 0)
-  out_shape = (*lead[:-1], kept) if drop else tuple(lead)
-  act = _normal_actions('normal_policy_loss', act, mean_raw)
-
-  def constant(name, value, shapes):
-    if not torch.is_tensor(value):
-      value = torch.as_tensor(np.asarray(value, np.float32))
-    if tuple(value.shape) not in shapes:
-      raise ValueError(f'normal_policy_loss: {name} of shape {tuple(value.shape)}, needs ' +
-                       ' or '.join(str(tuple(s)) for s in shapes))
-    return value.detach().to(device=mean_raw.device, dtype=torch.float32).contiguous()
-
-  adv = constant('adv', adv, (out_shape,))
-  weight = constant('weight', weight, (out_shape, tuple(lead)))
+  actent, n, t, drop, kept, out_shape = _loss_frame(who, 'inputs', mean_raw, lead, actent, drop_last)
+  act = _normal_actions(who, act, mean_raw)
+  adv = _loss_constant(who, 'adv', adv, (out_shape,), mean_raw.device)
+  weight = _loss_constant(who, 'weight', weight, (out_shape, tuple(lead)), mean_raw.device)
   if _normal_path(fused, n * t, actions) and n * kept > 0:
-    stride = weight.shape[-1] if drop else 1
-    loss, logpi, ent = _FusedNormalPolicy.apply(
-        mean_raw, std_raw, act, adv, weight, stride, (n, t, drop, actions), head, actent)
+    stride, geometry = weight.shape[-1] if drop else 1, (n, t, drop, actions)
+    loss, logpi, ent = _FusedNormalPolicy.apply(mean_raw, std_raw, act, adv, weight, stride, geometry, head, actent)
     return {'loss': loss.view(out_shape), 'logpi': logpi.view(out_shape), 'ent': ent.view(out_shape)}
-  if drop:      # the reference's [:, :-1], taken before the arithmetic instead of after: a dropped step takes no part
-    axis = len(lead) - 1
-    mean_raw, std_raw, act = (x.narrow(axis, 0, kept) for x in (mean_raw, std_raw, act))
-    weight = weight[..., :kept]
+  weight, mean_raw, std_raw, act = _kept_steps(lead, drop, kept, weight, mean_raw, std_raw, act)
   mean, std = _normal_moments(mean_raw, std_raw, *head)
-  logpi = _composed_normal_logp(mean, std, act, dims)
-  ent = _composed_normal_entropy(std, dims)
-  loss = weight * -(logpi * adv + actent * ent)
-  return {'loss': loss, 'logpi': logpi.detach(), 'ent': ent.detach()}
+  return _composed_loss(_composed_normal_logp(mean, std, act, dims), _composed_normal_entropy(std, dims), adv, weight,
+                        actent)

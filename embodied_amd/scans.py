@@ -151,10 +151,7 @@ PPO_TARGETS_FUSED_MAX = 16384
 
 def ppo_targets_launches():
   """Kernel launches `emb_ppo_targets` has issued in this process."""
-  import ctypes as C
-  count = C.c_int64(0)
-  api.emb_ppo_targets_launches(C.byref(count))
-  return count.value
+  return _lib.launches('ppo_targets')
 
 
 def _ppo_targets_path(fused, valnorm, advnorm, B, T):
@@ -306,10 +303,7 @@ DREAMER_TARGETS_FUSED_MAX = 16384
 
 def dreamer_targets_launches():
   """Kernel launches `emb_dreamer_targets` has issued in this process."""
-  import ctypes as C
-  count = C.c_int64(0)
-  api.emb_dreamer_targets_launches(C.byref(count))
-  return count.value
+  return _lib.launches('dreamer_targets')
 
 
 def _dreamer_targets_path(fused, retnorm, valnorm, advnorm, N, T):
