@@ -27,6 +27,8 @@ MODES = {'train': 0, 'report': 1, 'eval': 2}
 NORM_NONE, NORM_MEANSTD, NORM_PERC = 0, 1, 2
 EMB_RECON_MSE, EMB_RECON_MSE_SYMLOG, EMB_RECON_SIGMOID_MSE, EMB_RECON_BINARY = 0, 1, 2, 3
 NORMAL_BOUNDED, NORMAL_LOGSTD = 0, 1
+STAT_NONE, STAT_MUL_ADD, STAT_SUB_DIV = 0, 1, 2
+STAT_MAX_ENTRIES, STAT_VALUES = 48, 6      # EMB_STAT_MAX_ENTRIES, EMB_STAT_VALUES
 
 
 class EmbError(RuntimeError):
@@ -88,6 +90,17 @@ class BlockLinearPlan(C.Structure):
   _fields_ = [('forward', BlockLinearLaunch), ('grad_x', BlockLinearLaunch), ('grad_w', BlockLinearLaunch)] + [
       (name, C.c_int64) for name in (
           'splits', 'split_rows', 'launches_grad_w', 'sum_grid_x', 'workspace_bytes', 'workspace_max_multiple')]
+
+
+class StatEntry(C.Structure):
+  """emb_stat_entry_t: one matrix view of emb_stat_rows."""
+  _fields_ = [('x', C.c_void_p), ('affine', C.c_void_p), ('rows', C.c_int64), ('cols', C.c_int64),
+              ('stride', C.c_int64), ('mode', C.c_int32), ('weight', C.c_float)]
+
+
+class FillEntry(C.Structure):
+  """emb_fill_entry_t: one gradient buffer of emb_mean_fill."""
+  _fields_ = [('out', C.c_void_p), ('n', C.c_int64), ('scale', C.c_float), ('reserved', C.c_int32)]
 
 
 class SelectorCallbacks(C.Structure):
@@ -251,6 +264,9 @@ SIGNATURES = {
     'emb_normal_sample': [p, p, i32, i64, i64, i32, f32, f32, u64, u64, p, p, p],
     'emb_philox_normal': [u64, u64, u64, i64, p, p],
     'emb_normal_policy_launches': [p],
+    'emb_stat_rows': [p, i64, p, p, p],
+    'emb_mean_fill': [p, i64, p, p],
+    'emb_stat_rows_launches': [p],
     'emb_synth_env_step': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p],
     'emb_synth_env_step_masked': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p, p, i64, i32, p],
     'emb_env_mask_supported': [i64, i32],
@@ -391,6 +407,7 @@ class _FastApi:
       'emb_copy_bytes': 'ints', 'emb_mask_actions_notify': 'ints', 'emb_normalize': 'ints',
       'emb_ppo_targets': 'ppo_targets',
       'emb_scan_lambda_cont': 'scan_cont', 'emb_dreamer_targets': 'dreamer_targets',
+      'emb_stat_rows': 'ints', 'emb_mean_fill': 'ints',
   }
 
   def __init__(self, module):

@@ -1,6 +1,7 @@
 """Driver-side device ops: observation stack/transpose into the policy batch
 and per-env carry rows by env id (embodied/core/driver.py:65,
-embodied/jax/agent.py:173-181,230)."""
+embodied/jax/agent.py:173-181,230); and `stat_rows`, many small reductions in one
+launch (the kernels behind `scans.imag_metrics` and `outs.total_loss`)."""
 import numpy as np
 import torch
 
@@ -101,6 +102,79 @@ def rows_scatter(table, ids, rows):
   api.emb_rows_scatter(table.data_ptr(), rowbytes, _lib.ptr(ids), len(ids),
                        rows.data_ptr(), _stream(table))
   return table
+
+
+STAT_MODES = {None: _lib.STAT_NONE, 'none': _lib.STAT_NONE, 'mul_add': _lib.STAT_MUL_ADD,
+              'sub_div': _lib.STAT_SUB_DIV}
+STAT_COLUMNS = ('mean', 'std', 'absmean', 'min', 'max', 'rate')
+
+
+def stat_rows_launches():
+  """Kernel launches `emb_stat_rows` and `emb_mean_fill` have issued in this process."""
+  return _lib.launches('stat_rows')
+
+
+def stat_view(x):
+  """(rows, cols, row stride) of `x` as `emb_stat_rows` reads it, or None where it
+  is no such view: any contiguous tensor is one row; a 2-D tensor whose elements
+  follow each other along its rows (`x[:, :-1]` of a contiguous matrix) keeps its
+  rows and their stride."""
+  n = x.numel()
+  if x.is_contiguous():
+    return 1, n, n
+  if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1]:
+    return x.shape[0], x.shape[1], x.stride(0)
+  return None
+
+
+def stat_rows(entries, out=None):
+  """Six statistics of every entry, one launch per `_lib.STAT_MAX_ENTRIES` of them
+  (`emb_stat_rows`): -> (len(entries), 6) float32 with the columns `STAT_COLUMNS`
+  = mean, std (population), mean |x|, min, max and rate = count(|x| >= 1) / n.
+
+  An entry is a float32 CUDA tensor `x` that `stat_view` takes, or `(x, mode,
+  pair)` with mode 'mul_add' | 'sub_div' and `pair` a float32 CUDA tensor whose
+  first two elements are (offset, scale): the statistics are then those of
+  x * scale + offset or (x - offset) / scale, and the pair is read on the device
+  at the time the kernel runs (`DeviceNormalize`'s state words 3-4 go in as
+  `state[3:]`).  min and max return a NaN that is there, rate never counts one.
+  `out`: the caller's contiguous float32 (len(entries), 6) tensor."""
+  items = []
+  for entry in entries:
+    x, mode, pair = entry if isinstance(entry, (tuple, list)) else (entry, None, None)
+    if not (torch.is_tensor(x) and x.is_cuda):
+      raise RuntimeError('stat_rows runs as a HIP kernel: pass CUDA tensors (no CPU fallback)')
+    if mode not in STAT_MODES:
+      raise ValueError(f"stat_rows: mode {mode!r}, needs 'none', 'mul_add' or 'sub_div'")
+    view = stat_view(x)
+    if x.dtype != torch.float32 or view is None:
+      raise ValueError(
+          f'stat_rows: needs float32 tensors that are contiguous or 2-D with unit column stride, got {x.dtype} '
+          f'{tuple(x.shape)} with strides {tuple(x.stride())}')
+    mode = STAT_MODES[mode]
+    if mode != _lib.STAT_NONE and not (
+        torch.is_tensor(pair) and pair.device == x.device and pair.dtype == torch.float32 and pair.numel() >= 2
+        and pair.is_contiguous()):
+      raise ValueError('stat_rows: an affine entry needs its (offset, scale) as a contiguous float32 tensor on '
+                       "the entry's device")
+    items.append((x, view, mode, pair))
+  if not items:
+    raise ValueError('stat_rows: no entries')
+  dev = items[0][0].device
+  if any(x.device != dev for x, _, _, _ in items):
+    raise ValueError('stat_rows: the entries are on more than one device')
+  shape = (len(items), _lib.STAT_VALUES)
+  if out is None:
+    out = _lib.empty(shape, torch.float32, dev)
+  elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == shape
+            and out.device == dev and out.is_contiguous()):
+    raise ValueError(f'stat_rows(out=): needs a contiguous float32 {shape} tensor on {dev}')
+  table = (_lib.StatEntry * len(items))()
+  for entry, (x, (rows, cols, stride), mode, pair) in zip(table, items):
+    entry.x, entry.rows, entry.cols, entry.stride, entry.mode = x.data_ptr(), rows, cols, stride, mode
+    entry.affine = pair.data_ptr() if mode != _lib.STAT_NONE else None
+  fast.emb_stat_rows(table, len(items), out.data_ptr(), None, _stream(out))
+  return out
 
 
 class CuStream:

@@ -1659,3 +1659,116 @@ def normal_policy_loss(mean_raw, std_raw, act, adv, weight, actent=3e-4, kind='b
   mean, std = _normal_moments(mean_raw, std_raw, *head)
   return _composed_loss(_composed_normal_logp(mean, std, act, dims), _composed_normal_entropy(std, dims), adv, weight,
                         actent)
+
+
+# ------------------------------------------------------------ the loss total --
+# The largest loss (elements) up to which `total_loss(fused=None)` takes the
+# kernels: one workgroup reduces one loss, and one more reduces all of them again
+# for the total.  At both shapes of profiles/stat_metrics_bench.txt the fused
+# median is below the composed one -- K = 10 at (16, 64): forward 33.8 us against
+# 135.1 (1 device operation against 30), forward + backward 193.8 against 491.3 (3
+# against 51); at (64, 64): 36.9 against 164.5 and 127.9 against 396.4; every fused
+# figure is the host's enqueue time -- so the constant stays at what the kernels
+# index.  Nothing larger was measured.
+TOTAL_LOSS_FUSED_MAX = 2 ** 31 - 1
+TOTAL_LOSS_MAX_ELEMENTS = 2 ** 31 - 1
+
+
+def stat_rows_launches():
+  """Kernel launches `emb_stat_rows` and `emb_mean_fill` have issued in this process."""
+  return _lib.launches('stat_rows')
+
+
+def _total_loss_path(fused, float32, contiguous, count, smallest, largest):
+  """True: the kernels, False: the composed path (`total_loss` says when).
+  `float32`: every loss is a float32 CUDA tensor; `contiguous`: every one is;
+  `count` losses of `smallest` .. `largest` elements."""
+  fits = _fused_path(
+      'total_loss', fused,
+      (float32, 'the kernels read float32 CUDA tensors'),
+      (contiguous, 'the kernels read and write contiguous tensors'),
+      (count <= _lib.STAT_MAX_ENTRIES,
+       f'{count} losses, the total is formed by one launch of at most {_lib.STAT_MAX_ENTRIES} entries'),
+      (smallest >= 1, 'a loss without elements (its mean is NaN)'),
+      (largest <= TOTAL_LOSS_MAX_ELEMENTS, f'a loss of {largest} elements, the kernels index at most 2^31 - 1'))
+  if fused is None:
+    return fits and largest <= TOTAL_LOSS_FUSED_MAX
+  return fits
+
+
+class _FusedTotal(torch.autograd.Function):
+  """(total, stats (K, 6)) of K losses: one launch forward (`emb_stat_rows` with
+  its total), one backward (`emb_mean_fill`).  Only `total` carries a gradient."""
+
+  @staticmethod
+  def forward(ctx, scales, *losses):
+    device = losses[0].device
+    count = len(losses)
+    flat = _lib.empty((count * _lib.STAT_VALUES + 1,), torch.float32, device)
+    stats, total = flat[:-1].view(count, _lib.STAT_VALUES), flat[-1]
+    table = (_lib.StatEntry * count)()
+    for entry, scale, v in zip(table, scales, losses):
+      n = v.numel()
+      entry.x, entry.rows, entry.cols, entry.stride, entry.weight = v.data_ptr(), 1, n, n, scale
+    _lib.fast.emb_stat_rows(table, count, stats.data_ptr(), total.data_ptr(), _lib.raw_stream(device))
+    ctx.saved = (scales, [v.shape for v in losses], device)
+    ctx.set_materialize_grads(False)
+    ctx.mark_non_differentiable(stats)
+    return total, stats
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout, _stats):
+    scales, shapes, device = ctx.saved
+    wanted = [k for k, need in enumerate(ctx.needs_input_grad[1:]) if need]
+    if gout is None or not wanted:
+      return (None,) * (1 + len(shapes))
+    gout = gout.to(torch.float32).contiguous()
+    # one allocation; every gradient starts on a 16-byte boundary (the kernel's wide stores)
+    sizes = [(shapes[k].numel() + 3) // 4 * 4 for k in wanted]
+    flat = _lib.empty((sum(sizes),), torch.float32, device)
+    table = (_lib.FillEntry * len(wanted))()
+    grads, start = [None] * len(shapes), 0
+    for entry, k, size in zip(table, wanted, sizes):
+      n = shapes[k].numel()
+      grads[k] = flat[start:start + n].view(shapes[k])
+      entry.out, entry.n, entry.scale = grads[k].data_ptr(), n, scales[k]
+      start += size
+    _lib.fast.emb_mean_fill(table, len(wanted), gout.data_ptr(), _lib.raw_stream(device))
+    return (None, *grads)
+
+
+def total_loss(losses, scales, fused=None):
+  """The end of Agent.loss (dreamerv3/agent.py:237-240) -> (loss, metrics):
+  metrics[f'loss/{k}'] = losses[k].mean(), detached, and loss =
+  sum([losses[k].mean() * scales[k] ...]) -- a 0-d float32 with autograd, the
+  products added in dict order in float32 from 0, as Python's `sum` does.
+  `losses` is a dict of tensors of any shape, `scales` a dict of numbers with the
+  same keys (ValueError otherwise: the reference's assert, agent.py:237).
+  Two paths compute it:
+    composed  torch's `mean`, multiply and add: every dtype, every layout.  The
+              definition.
+    fused     float32 contiguous CUDA losses, at most 48 of them: ONE launch
+              forward (a workgroup per loss writes its mean; one more reduces
+              every loss again and adds the products, so no result depends on the
+              order in which workgroups finish) and ONE backward, which writes
+              (g * scales[k]) / n_k into every loss's gradient.  The metrics are
+              views of the launch's result buffer, which this call allocates.
+  `fused=None` takes the kernels where they fit and no loss is larger than
+  TOTAL_LOSS_FUSED_MAX; True / False force a path (True raises where they do not
+  fit, and says why).  A NaN or infinity in one loss shows in its own `loss/{k}`
+  and in the total, and in nothing else."""
+  if set(losses) != set(scales):
+    raise ValueError(f'total_loss: losses {sorted(losses)} and scales {sorted(scales)} do not have the same keys')
+  if not losses:
+    raise ValueError('total_loss: no losses')
+  values = list(losses.values())
+  float32 = all(torch.is_tensor(v) and v.is_cuda and v.dtype == torch.float32 for v in values)
+  sizes = [v.numel() for v in values]
+  if not _total_loss_path(fused, float32, all(v.is_contiguous() for v in values), len(values), min(sizes), max(sizes)):
+    means = {k: v.mean() for k, v in losses.items()}
+    loss = sum([means[k] * scales[k] for k in losses])
+    return loss, {f'loss/{k}': mean.detach() for k, mean in means.items()}
+  weights = tuple(float(np.float32(scales[k])) for k in losses)
+  total, stats = _FusedTotal.apply(weights, *values)
+  return total, {f'loss/{k}': stats[index, 0] for index, k in enumerate(losses)}

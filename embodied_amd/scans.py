@@ -435,6 +435,173 @@ def dreamer_targets(rew, con, pred, retnorm, valnorm, advnorm, contdisc=True, ho
   return DreamerTargets(ret, weight, adv, adv_normed, tar_padded)
 
 
+# The largest array (elements) up to which `imag_metrics(fused=None)` takes the
+# kernel.  An entry is reduced by ONE workgroup, so a large array could lose to
+# torch's many; at every shape of profiles/stat_metrics_bench.txt the fused median
+# is below the composed one -- (16, 16) 26.1 us against 210.3, (1024, 16) 22.6
+# against 187.7, (1024, 17) 20.9 against 137.3, and (4096, 16), past what
+# `dreamer_targets` fuses, 24.4 against 204.4 (31 device operations composed, 1
+# fused; the fused figure is the host's enqueue time at all but the last) -- so
+# the constant stays at what the kernel indexes.  Nothing larger was measured.
+IMAG_METRICS_FUSED_MAX = 2 ** 31 - 1
+IMAG_METRICS = ('adv', 'adv_std', 'adv_mag', 'rew', 'con', 'ret', 'val', 'tar', 'weight', 'slowval',
+                'ret_min', 'ret_max', 'ret_rate')
+
+
+def _imag_metrics_path(fused, float32, views, largest):
+  """True: the kernel, False: the composed path (`imag_metrics` says when).
+  `float32`: every input is a float32 CUDA tensor; `views`: every one is a matrix
+  view `emb_stat_rows` takes; `largest`: the elements of the largest of them."""
+  from . import outs
+  fits = outs._fused_path(
+      'imag_metrics', fused,
+      (float32, 'the kernel reads float32 CUDA tensors'),
+      (views, 'the kernel reads arrays that are contiguous, or 2-D with unit column stride'),
+      (largest <= 2 ** 31 - 1, f'an array of {largest} elements, the kernel indexes at most 2^31 - 1'))
+  if fused is None:
+    return fits and largest <= IMAG_METRICS_FUSED_MAX
+  return fits
+
+
+_STAT_PAIRS, _IMAG_PLANS = {}, {}
+
+
+def _constant_pair(offset, scale, dev):
+  """(offset, scale) as a float32 pair on `dev`, uploaded once per value."""
+  key = (offset, scale, dev)
+  pair = _STAT_PAIRS.get(key)
+  if pair is None:
+    if len(_STAT_PAIRS) > 256:
+      _STAT_PAIRS.clear()
+    pair = _STAT_PAIRS[key] = torch.tensor([offset, scale], dtype=torch.float32, device=dev)
+  return pair
+
+
+def _device_pair(offset, scale, dev):
+  """The (offset, scale) of an affine entry: None for the constants (0, 1), else a
+  float32 tensor on `dev` that holds the two side by side -- two 0-d views of
+  neighbouring words (a clone of `DeviceNormalize`'s state words 3-4) as they
+  are, anything else packed by one torch op."""
+  if torch.is_tensor(offset) or torch.is_tensor(scale):
+    if (torch.is_tensor(offset) and torch.is_tensor(scale) and offset.device == dev and scale.device == dev
+        and offset.dtype == scale.dtype == torch.float32 and offset.numel() == scale.numel() == 1
+        and scale.data_ptr() == offset.data_ptr() + 4):
+      return torch.as_strided(offset, (2,), (1,))
+    parts = [torch.as_tensor(v, dtype=torch.float32, device=dev).reshape(()) for v in (offset, scale)]
+    return torch.stack(parts)
+  offset, scale = float(offset), float(scale)
+  if offset == 0.0 and scale == 1.0:
+    return None
+  return _constant_pair(offset, scale, dev)
+
+
+def imag_metrics(targets, rew, con, val_pred, slow_pred, retnorm, vstats=None, ents=None, entlimits=None,
+                 fused=None):
+  """The metrics of imag_loss (dreamerv3/agent.py:424-442) -> {name: 0-d float32}:
+  adv, adv_std (population), adv_mag; rew, con, weight; ret, ret_min, ret_max and
+  ret_rate of ret_normed = (ret - roffset) / rscale; val and slowval, the means of
+  pred * vscale + voffset; tar, the mean of `tar_padded[:, :-1]`; and per action
+  key `ent/{k}`, the mean of `ents[k][:, :-1]`, with `rand/{k}` =
+  (ent - minent) / (maxent - minent) where `entlimits` has the key.
+
+  targets   the `DreamerTargets` of the same train step
+  rew, con, val_pred, slow_pred  (N, T): `value.pred()` and `slowvalue.pred()`
+  retnorm   the `DeviceNormalize` that `dreamer_targets` just stepped: its
+            (offset, scale) is what `retnorm(ret, update)` returned, read from the
+            state words ON THE DEVICE; 'none' is the constants (0, 1)
+  vstats    valnorm's (voffset, vscale) from BEFORE the step (agent.py:397), as
+            floats or 0-d device tensors; None is (0, 1), the shipped
+            `valnorm: none`.  `dreamer_targets` overwrites a 'meanstd' valnorm's
+            words in place: a caller with one must CLONE `valnorm.latest()`
+            before calling `dreamer_targets`, and pass the clones
+  ents      {key: (N, T) float32 entropy}; the `[:, :-1]` is taken by stride
+  entlimits {key: (minent, maxent)}
+
+  T < 2 or N = 0 raises ValueError (the reference would take means of nothing).
+  Two paths compute it:
+    composed  torch ops, one by one as the reference writes them: every dtype,
+              every layout.  The definition.
+    fused     ONE launch of `emb_stat_rows` for up to 48 entries (8 arrays, one
+              more per key and one more per key with limits; more keys: further
+              launches); float32 inputs.  `rand/{k}` is the mean of
+              (ent - minent) / (maxent - minent), a second entry over the same
+              array, so it costs no launch.
+  `fused=None` takes the kernel where it fits and no array is larger than
+  IMAG_METRICS_FUSED_MAX; True / False force a path (True raises where it does
+  not fit, and says why).  The fused results are 0-d VIEWS of one result buffer
+  per argument structure: valid in stream order until the next call with the same
+  structure, which overwrites them in place (clone them to keep a value)."""
+  ret, weight, adv, tar_padded = targets.ret, targets.weight, targets.adv, targets.tar_padded
+  if rew.dim() != 2:
+    raise ValueError(f'imag_metrics: rew must be (N, T), got {tuple(rew.shape)}')
+  N, T = rew.shape
+  if N == 0 or T < 2:
+    raise ValueError(f'imag_metrics: (N, T) = ({N}, {T}), needs N >= 1 and T >= 2 (means of empty arrays otherwise)')
+  ents = dict(ents or {})
+  entlimits = dict(entlimits or {})
+  if not set(entlimits) <= set(ents):
+    raise ValueError(f'imag_metrics: entlimits for {sorted(set(entlimits) - set(ents))}, which `ents` does not have')
+  wide, short = (rew, con, val_pred, slow_pred, weight, tar_padded, *ents.values()), (ret, adv)
+  if any(tuple(x.shape) != (N, T) for x in wide) or any(tuple(x.shape) != (N, T - 1) for x in short):
+    raise ValueError(f'imag_metrics: needs ({N}, {T}) arrays and ({N}, {T - 1}) returns and advantages')
+  from . import ops
+  arrays = wide + short
+  float32 = all(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 for x in arrays)
+  views = all(ops.stat_view(x) is not None for x in arrays)
+  voffset, vscale = (0.0, 1.0) if vstats is None else vstats
+  if not _imag_metrics_path(fused, float32, views, N * T):
+    roffset, rscale = retnorm.latest()
+    ret_normed = (ret - roffset) / rscale
+    val, slowval = val_pred * vscale + voffset, slow_pred * vscale + voffset
+    metrics = {
+        'adv': adv.mean(), 'adv_std': adv.std(correction=0), 'adv_mag': adv.abs().mean(),
+        'rew': rew.mean(), 'con': con.mean(), 'ret': ret_normed.mean(), 'val': val.mean(),
+        'tar': tar_padded[:, :-1].mean(), 'weight': weight.mean(), 'slowval': slowval.mean(),
+        'ret_min': ret_normed.min(), 'ret_max': ret_normed.max(),
+        # (a count over n as a true division: torch's mean multiplies by a rounded 1 / n)
+        'ret_rate': (ret_normed.abs() >= 1.0).sum().to(torch.float32) / _disc_tensor(float(ret.numel()), ret.device)}
+    for k, ent in ents.items():
+      metrics[f'ent/{k}'] = ent[:, :-1].mean()
+      if k in entlimits:
+        lo, hi = entlimits[k]
+        metrics[f'rand/{k}'] = (metrics[f'ent/{k}'] - lo) / (hi - lo)
+    return {k: v if v.dtype == torch.float32 else v.to(torch.float32) for k, v in metrics.items()}
+  dev = rew.device
+  if retnorm.impl == 'none':
+    rpair = None
+  else:
+    retnorm.latest()                          # words 3-4 hold (offset, scale) of the present statistics
+    rpair = retnorm._state(dev)[3:]
+  vpair = _device_pair(voffset, vscale, dev)
+  sub, mul = _lib.STAT_SUB_DIV, _lib.STAT_MUL_ADD
+  items = [(adv, 0, None), (rew, 0, None), (con, 0, None), (ret, sub if rpair is not None else 0, rpair),
+           (val_pred, mul if vpair is not None else 0, vpair), (slow_pred, mul if vpair is not None else 0, vpair),
+           (tar_padded[:, :-1], 0, None), (weight, 0, None)]
+  names = {'adv': (0, 0), 'adv_std': (0, 1), 'adv_mag': (0, 2), 'rew': (1, 0), 'con': (2, 0), 'ret': (3, 0),
+           'val': (4, 0), 'tar': (6, 0), 'weight': (7, 0), 'slowval': (5, 0), 'ret_min': (3, 3), 'ret_max': (3, 4),
+           'ret_rate': (3, 5)}
+  for k, ent in ents.items():
+    names[f'ent/{k}'] = (len(items), 0)
+    items.append((ent[:, :-1], 0, None))
+    if k in entlimits:
+      lo, hi = (float(v) for v in entlimits[k])
+      names[f'rand/{k}'] = (len(items), 0)
+      items.append((ent[:, :-1], sub, _constant_pair(lo, hi - lo, dev)))
+  key = (dev, tuple(names))
+  plan = _IMAG_PLANS.get(key)
+  if plan is None:
+    if len(_IMAG_PLANS) > 64:
+      _IMAG_PLANS.clear()
+    out = torch.empty((len(items), _lib.STAT_VALUES), dtype=torch.float32, device=dev)
+    plan = _IMAG_PLANS[key] = ((_lib.StatEntry * len(items))(), out, {k: out[e, c] for k, (e, c) in names.items()})
+  table, out, results = plan
+  for entry, (x, mode, pair) in zip(table, items):
+    entry.rows, entry.cols, entry.stride = ops.stat_view(x)
+    entry.x, entry.mode, entry.affine = x.data_ptr(), mode, None if pair is None else pair.data_ptr()
+  fast.emb_stat_rows(table, len(items), out.data_ptr(), None, _stream(rew))
+  return dict(results)
+
+
 _MULTI = {}
 
 

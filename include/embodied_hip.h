@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports (152 functions). */
+ * it exports (155 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -52,7 +52,8 @@ extern "C" {
  * emb_onehot_sample_launches, emb_recon_loss, emb_recon_loss_grad,
  * emb_recon_loss_launches, emb_normal_policy_loss, emb_normal_policy_loss_grad,
  * emb_normal_sample, emb_philox_normal, emb_normal_policy_launches,
- * emb_block_linear_plan (additions only).                                      */
+ * emb_block_linear_plan, emb_stat_rows, emb_stat_rows_launches, emb_mean_fill
+ * (additions only).                                                           */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -1104,6 +1105,72 @@ int32_t emb_philox_normal(uint64_t seed, uint64_t offset, uint64_t first, int64_
 /* Kernel launches the four entry points above have issued in this process,
  * counted where the kernels are launched.                                      */
 int32_t emb_normal_policy_launches(int64_t* count);
+
+/* ---- device metrics: many small reductions in one launch, float32 on device --
+ * The scalar book-keeping of a DreamerV3 train step.  One kernel family serves
+ *   dreamerv3/agent.py:424-442  the metrics of imag_loss: adv.mean(), adv.std(),
+ *                               |adv|.mean(), the means of rew, con, val, slowval,
+ *                               tar_normed, weight and of every ents[k]; mean,
+ *                               min, max and (|.| >= 1).mean() of
+ *                               ret_normed = (ret - roffset) / rscale
+ *   dreamerv3/agent.py:239-240  loss/{k} = v.mean() and
+ *                               loss = sum([v.mean() * scales[k] ...])
+ * in place of 25 to 30 torch launches each way.
+ *
+ * An entry is a float32 matrix view: `x`, rows >= 1, cols >= 1 and a row stride
+ * in elements >= cols (x[:, :-1] of a contiguous (N, T) is cols = T - 1,
+ * stride = T: no copy).  With a mode other than EMB_STAT_NONE the statistics are
+ * those of x' = x * scale + offset (EMB_STAT_MUL_ADD) or (x - offset) / scale
+ * (EMB_STAT_SUB_DIV, a true division), float32 operations in that order, where
+ * `affine` is the DEVICE address of the float32 pair (offset, scale), read by
+ * the kernel: words 3-4 of an emb_normalize state go in as they are.
+ * emb_stat_rows gives every entry one workgroup, which writes
+ *   out[e, 0] mean    out[e, 1] std (population, jnp.std)    out[e, 2] mean |x'|
+ *   out[e, 3] min     out[e, 4] max    out[e, 5] rate = count(|x'| >= 1) / n
+ * Sums are float64 in a fixed order without atomics: the same bits run to run
+ * for the same inputs at the same addresses (a contiguous entry on a 16-byte
+ * boundary is read with 16-byte loads, any other with 4-byte loads, which may
+ * round a sum differently).  min and max return a NaN that is there (jnp.min,
+ * jnp.max); a NaN never counts toward rate; a NaN or infinity in entry e
+ * changes row e only.  One launch per EMB_STAT_MAX_ENTRIES entries; `out` is
+ * (count, EMB_STAT_VALUES) float32.
+ * `total` (NULL: none), agent.py:240: one more workgroup of the same launch
+ * reduces every entry again and writes total[0] = 0 + out[0, 0] * weight_0 +
+ * out[1, 0] * weight_1 + ..., float32, left to right as Python's sum(); it reads
+ * no other workgroup's result, so its bits do not depend on their order.
+ * EMB_ERR_INVALID before any HIP call: count < 0, and with count > 0 a NULL
+ * `entries` or `out`, rows or cols < 1, stride < cols, an entry of more than
+ * 2^31 - 1 elements, an unknown mode, a NULL `x` (or `affine` where the mode
+ * reads it), an address off 4 bytes, `total` with more than
+ * EMB_STAT_MAX_ENTRIES entries.  count = 0: EMB_OK, nothing is launched.        */
+#define EMB_STAT_NONE 0
+#define EMB_STAT_MUL_ADD 1
+#define EMB_STAT_SUB_DIV 2
+#define EMB_STAT_MAX_ENTRIES 48
+#define EMB_STAT_VALUES 6
+typedef struct emb_stat_entry {
+  const void* x;
+  const void* affine;
+  int64_t rows, cols, stride;
+  int32_t mode;
+  float weight;
+} emb_stat_entry_t;
+int32_t emb_stat_rows(const emb_stat_entry_t* entries, int64_t count, void* out, void* total, void* stream);
+/* The backward of agent.py:239-240: out_k[i] = (g[0] * scale_k) / n_k for every
+ * element of every entry, `g` the device address of the float32 gradient of the
+ * loss; one launch per EMB_STAT_MAX_ENTRIES entries.  EMB_ERR_INVALID before
+ * any HIP call: count < 0, and with count > 0 a NULL `entries`, `g` or `out`, an
+ * address off 4 bytes, n < 1 or n > 2^31 - 1.                                   */
+typedef struct emb_fill_entry {
+  void* out;
+  int64_t n;
+  float scale;
+  int32_t reserved;
+} emb_fill_entry_t;
+int32_t emb_mean_fill(const emb_fill_entry_t* entries, int64_t count, const void* g, void* stream);
+/* Kernel launches the two entry points above have issued in this process,
+ * counted where the kernels are launched.                                      */
+int32_t emb_stat_rows_launches(int64_t* count);
 
 /* ----------------------------------------------------------- collectives --
  * The two exchange steps of the sharded path on RCCL directly (xGMI inside one
