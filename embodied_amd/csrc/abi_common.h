@@ -134,6 +134,17 @@ inline void need(bool ok, const char* msg) {
   if (!ok) throw std::invalid_argument(msg);
 }
 
+// need()'s message with the entry point's name in front: `const Who say{who};`
+// then need(ok, say("what")) refuses with "who: what".  The text lives in one
+// thread-local string until the next call; need() copies it when it throws.
+struct Who {
+  const char* who;
+  const char* operator()(const char* what) const {
+    static thread_local std::string msg;
+    return (msg = std::string(who) + ": " + what).c_str();
+  }
+};
+
 // Ticks of the time-stamp counter per microsecond, measured (not assumed): one
 // (tsc, CLOCK_MONOTONIC) pair when the library is loaded, a second one at the
 // first question -- at least 200 us later, waited for if need be.

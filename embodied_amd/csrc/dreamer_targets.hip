@@ -10,12 +10,11 @@
 //
 // One workgroup, because the select wants every key in one LDS: the launch
 // takes N * (T-1) <= kNormLdsMax values (scans.py composes larger ones).
+#include "wave_util.h"          // LaunchCount; sets no fp-contract mode
 #include "scan_segment.h"       // the scan keeps scans.hip's arithmetic (its multiply-adds may contract)
 #include "dreamer_targets.h"
 #include "normalize_device.h"   // from here on float32 operations one by one, as normalize.hip
 #include "norm_select.h"
-
-#include <atomic>
 
 namespace emb {
 namespace {
@@ -225,11 +224,11 @@ __global__ __launch_bounds__(kNormThreads) void dreamer_targets_kernel(const Dre
   }
 }
 
-std::atomic<int64_t> g_launches{0};
+segment::LaunchCount g_count;
 
 }  // namespace
 
-int64_t dreamer_targets_launches() { return g_launches.load(std::memory_order_relaxed); }
+int64_t dreamer_targets_launches() { return g_count.value(); }
 
 hipError_t launch_dreamer_targets(const float* rew, const float* con, const float* pred, int64_t N, int64_t T,
                                   float disc, float lam, bool update, float* ret, float* weight, float* adv,
@@ -268,9 +267,7 @@ hipError_t launch_dreamer_targets(const float* rew, const float* con, const floa
     default: EMB_DREAMER_TARGETS(64); break;
   }
 #undef EMB_DREAMER_TARGETS
-  const hipError_t status = hipGetLastError();
-  if (status == hipSuccess) g_launches.fetch_add(1, std::memory_order_relaxed);   // the only launch site of this file
-  return status;
+  return g_count.launched();
 }
 
 }  // namespace emb

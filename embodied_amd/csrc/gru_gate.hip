@@ -13,9 +13,7 @@
 // the host), the grid is capped and strides.  Elementwise: a NaN or a saturated
 // gate touches its own element alone.
 #include "gru_gate.h"
-#include "onehot_segment.h"
-
-#include <atomic>
+#include "wave_util.h"
 
 // float32 operations one by one, as twohot.hip
 #pragma clang fp contract(off)
@@ -27,11 +25,6 @@ constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;                  // 8 workgroups on each of 256 CUs; more elements: grid stride
 
 using namespace segment;
-
-__device__ __forceinline__ uint32_t bf16_bits(float v) {           // as segment::store
-  const uint32_t u = __float_as_uint(v);
-  return v != v ? ((u >> 16) | 0x40u) : ((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
 
 // E elements of T at p: one 16-byte access (E = 16 / sizeof(T)) or one element (E = 1)
 template <int E>
@@ -70,14 +63,12 @@ __device__ __forceinline__ void store_n(bf16_t* p, const float (&v)[E]) {
   if constexpr (E == 8) {
     uint32_t w[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) w[k] = (bf16_bits(v[2 * k]) & 0xffffu) | (bf16_bits(v[2 * k + 1]) << 16);
+    for (int k = 0; k < 4; ++k) w[k] = bf16_bits(v[2 * k]) | (static_cast<uint32_t>(bf16_bits(v[2 * k + 1])) << 16);
     *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
   } else {
     store(p, 0, v[0]);
   }
 }
-
-__device__ __forceinline__ float sigmoid(float x) { return 1.f / (1.f + expf(-x)); }     // jax.nn.sigmoid
 
 // Where item i (E outputs) sits: `at` in deter / out, `gate` in x (its reset; cand
 // and update are h and 2h further), rssm.py:153-154.  All below 2^31.
@@ -155,7 +146,7 @@ __global__ __launch_bounds__(kThreads) void gru_gate_grad_kernel(const T* __rest
   }
 }
 
-std::atomic<int64_t> g_launches{0};
+LaunchCount g_count;
 
 bool fits(int64_t rows, int64_t width, int64_t blocks) {
   return rows >= 1 && width >= 1 && blocks >= 1 && width % blocks == 0 && width <= INT32_MAX / 3 &&
@@ -169,15 +160,9 @@ int grid_of(int64_t items) {
   return static_cast<int>(blocks < kMaxBlocks ? blocks : kMaxBlocks);
 }
 
-hipError_t launched() {
-  const hipError_t status = hipGetLastError();
-  if (status == hipSuccess) g_launches.fetch_add(1, std::memory_order_relaxed);
-  return status;
-}
-
 }  // namespace
 
-int64_t gru_gate_launches() { return g_launches.load(std::memory_order_relaxed); }
+int64_t gru_gate_launches() { return g_count.value(); }
 
 hipError_t launch_gru_gate(const void* x, const void* deter, bool bf16, int64_t rows, int64_t width, int64_t blocks,
                            void* out, hipStream_t stream) {
@@ -193,7 +178,7 @@ hipError_t launch_gru_gate(const void* x, const void* deter, bool bf16, int64_t 
   else if (vec) EMB_GATE(float, 4);
   else EMB_GATE(float, 1);
 #undef EMB_GATE
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_gru_gate_grad(const void* x, const void* deter, const void* gout, bool bf16, int64_t rows,
@@ -212,7 +197,7 @@ hipError_t launch_gru_gate_grad(const void* x, const void* deter, const void* go
   else if (vec) EMB_GATE_GRAD(float, 4);
   else EMB_GATE_GRAD(float, 1);
 #undef EMB_GATE_GRAD
-  return launched();
+  return g_count.launched();
 }
 
 }  // namespace emb

@@ -12,8 +12,7 @@ namespace {
 
 // What both entry points check before any HIP call.
 void shape_ok(const char* who, int32_t dtype, int64_t rows, int64_t deter, int64_t blocks) {
-  static thread_local std::string msg;
-  auto say = [&](const char* what) { return (msg = std::string(who) + ": " + what).c_str(); };
+  const Who say{who};
   need(dtype == EMB_F32 || dtype == EMB_BF16, say("dtype must be EMB_F32 or EMB_BF16"));
   need(rows >= 0, say("negative rows"));
   need(deter >= 1, say("deter must be at least 1"));

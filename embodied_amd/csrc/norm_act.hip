@@ -9,7 +9,7 @@
 // With torch ops the forward alone is a chain of about eight launches.
 //
 // A row belongs to TPR threads, each holding PER of its values: one wave64 up to
-// 1024 units (4 rows per workgroup, butterflies of onehot_segment.h and nothing
+// 1024 units (4 rows per workgroup, butterflies of wave_util.h and nothing
 // else), a workgroup of 256 up to 8192 (the waves' sums meet in LDS, added in the
 // order of the waves).  Up to 16 384 the forward takes a workgroup of 1024, 16
 // values per thread; the gradient there keeps nothing: a workgroup of 256 passes
@@ -18,9 +18,7 @@
 // (4 float32, 8 bfloat16) where `units` is a multiple of that and every pointer is
 // aligned, and element by element otherwise.  No atomics: the same bits run to run.
 #include "norm_act.h"
-#include "onehot_segment.h"
-
-#include <atomic>
+#include "wave_util.h"
 
 // float32 operations one by one, as twohot.hip
 #pragma clang fp contract(off)
@@ -35,13 +33,6 @@ constexpr int kReduceCols = 32, kReduceParts = kBlock / kReduceCols;
 
 using namespace segment;
 static_assert(kWave == kLanes, "the segment helpers shuffle over one wave64");
-
-__device__ __forceinline__ float quiet_nan() { return __uint_as_float(0x7fc00000u); }
-
-__device__ __forceinline__ uint32_t bf16_bits(float v) {           // as segment::store
-  const uint32_t u = __float_as_uint(v);
-  return v != v ? ((u >> 16) | 0x40u) : ((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
 
 // E = 16 bytes of T, at an address that is a multiple of 16
 __device__ __forceinline__ void load16(const float* p, float* v) {
@@ -63,7 +54,7 @@ __device__ __forceinline__ void store16(float* p, const float* v) {
 __device__ __forceinline__ void store16(bf16_t* p, const float* v) {
   uint32_t w[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) w[k] = (bf16_bits(v[2 * k]) & 0xffffu) | (bf16_bits(v[2 * k + 1]) << 16);
+  for (int k = 0; k < 4; ++k) w[k] = bf16_bits(v[2 * k]) | (static_cast<uint32_t>(bf16_bits(v[2 * k + 1])) << 16);
   *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
@@ -174,8 +165,6 @@ __device__ __forceinline__ void row_sum2(float& a, float& b, float* lds) {
     __syncthreads();
   }
 }
-
-__device__ __forceinline__ float sigmoid(float x) { return 1.f / (1.f + expf(-x)); }     // jax.nn.sigmoid
 
 constexpr float kSqrt2OverPi = 0.7978845608028654f, kGeluCubic = 0.044715f;                 // jax.nn.gelu, approximate
 
@@ -496,7 +485,7 @@ __global__ __launch_bounds__(kBlock) void norm_act_reduce_kernel(const float* __
   }
 }
 
-std::atomic<int64_t> g_launches{0};
+LaunchCount g_count;
 
 bool fits(int64_t rows, int64_t units, int32_t impl, int32_t act) {
   return rows >= 1 && units >= 1 && units <= kNormActMaxUnits && rows <= INT32_MAX / units &&
@@ -504,12 +493,6 @@ bool fits(int64_t rows, int64_t units, int32_t impl, int32_t act) {
 }
 
 bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
-hipError_t launched() {
-  const hipError_t status = hipGetLastError();
-  if (status == hipSuccess) g_launches.fetch_add(1, std::memory_order_relaxed);
-  return status;
-}
 
 // threads per row and values per thread by the row's width
 #define EMB_NORM_BY_WIDTH(CALL, u)            \
@@ -539,7 +522,7 @@ int rows_per_block(int64_t units) { return units <= kNormActWaveUnits ? kBlock /
 
 }  // namespace
 
-int64_t norm_act_launches() { return g_launches.load(std::memory_order_relaxed); }
+int64_t norm_act_launches() { return g_count.value(); }
 
 hipError_t launch_norm_act(const void* x, const float* scale, const float* shift, bool bf16, int64_t rows,
                            int64_t units, int32_t impl, int32_t act, float eps, void* out, hipStream_t stream) {
@@ -559,7 +542,7 @@ hipError_t launch_norm_act(const void* x, const float* scale, const float* shift
   EMB_NORM_BY_WIDTH(EMB_FORWARD, units);
 #undef EMB_FORWARD
 #undef EMB_FORWARD_AS
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_norm_act_grad(const void* x, const float* scale, const float* shift, const void* gout, bool bf16,
@@ -596,12 +579,12 @@ hipError_t launch_norm_act_grad(const void* x, const float* scale, const float* 
 #undef EMB_GRAD_WIDE
 #undef EMB_GRAD
 #undef EMB_GRAD_AS
-  hipError_t status = launched();
+  hipError_t status = g_count.launched();
   if (status != hipSuccess || !params) return status;
   const dim3 rgrid(static_cast<unsigned>((units + kReduceCols - 1) / kReduceCols), 2);
   hipLaunchKernelGGL(norm_act_reduce_kernel, rgrid, dim3(kBlock), 0, stream, part, dscale, dshift,
                      static_cast<int32_t>(grid.x), u);
-  return launched();
+  return g_count.launched();
 }
 
 }  // namespace emb

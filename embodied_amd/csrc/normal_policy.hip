@@ -23,8 +23,6 @@
 #include "onehot_segment.h"
 #include "philox.h"
 
-#include <atomic>
-
 // float32 operations one by one, as twohot.hip
 #pragma clang fp contract(off)
 
@@ -40,10 +38,6 @@ static_assert(kWave == kLanes, "the segment helpers shuffle over one wave64");
 
 constexpr float kHalfLog2Pi = 0.91893853320467274178f;     // log(2 pi) / 2
 constexpr float kTwoPi = 6.28318530717958647692f;
-
-__device__ __forceinline__ float nan_value() { return __uint_as_float(0x7fc00000u); }
-
-__device__ __forceinline__ float sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // heads.py:151-152 / heads.py:161
 __device__ __forceinline__ void moments(bool bounded, float m, float s, float lo, float span, float& mean, float& std) {
@@ -84,10 +78,10 @@ __global__ __launch_bounds__(kThreads) void normal_policy_loss_kernel(
           const float a = act[at + i];
           const float z = (a - mean) / std;
           lp = lp + ((-(z * z) * 0.5f - logf(std)) - kHalfLog2Pi);             // outs.py:174-176
-          if (a != a) flag = nan_value();
+          if (a != a) flag = quiet_nan();
         }
         e = e + (0.5f * logf(kTwoPi * (std * std)) + 0.5f);                    // outs.py:178-179
-        if (m != m || s != s) flag = nan_value();
+        if (m != m || s != s) flag = quiet_nan();
       }
     }
     lp = seg_sum<W>(lp);                                           // Agg's sum over the action dimensions, outs.py:63-64, 69-71
@@ -134,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void normal_policy_loss_grad_kernel(
         m[j] = load(mean_raw, at + i);
         s[j] = load(std_raw, at + i);
         if (act) a[j] = act[at + i];
-        if (m[j] != m[j] || s[j] != s[j] || a[j] != a[j]) flag = nan_value();
+        if (m[j] != m[j] || s[j] != s[j] || a[j] != a[j]) flag = quiet_nan();
       }
     }
     flag = seg_sum<W>(flag);                                       // NaN if any element of the row is
@@ -202,7 +196,7 @@ __global__ __launch_bounds__(kThreads) void normal_sample_kernel(
   }
 }
 
-std::atomic<int64_t> g_launches{0};
+LaunchCount g_count;
 
 bool fits(int64_t N, int64_t T, int64_t drop, int64_t A, int kind, float lo, float hi) {
   if (kind != kNormalBounded && kind != kNormalLogstd) return false;
@@ -229,29 +223,16 @@ int flat_blocks(int64_t count) {
   return static_cast<int>(blocks < kNormalMaxBlocks ? blocks : kNormalMaxBlocks);
 }
 
-hipError_t launched() {
-  const hipError_t status = hipGetLastError();
-  if (status == hipSuccess) g_launches.fetch_add(1, std::memory_order_relaxed);
-  return status;
-}
-
-// the narrowest segment that holds a row, then 2 or 4 values per lane of the whole wave
-#define EMB_NORMAL_BY_WIDTH(CALL, a)     \
-  do {                                   \
-    if ((a) <= 1) { CALL(1, 1); }        \
-    else if ((a) <= 2) { CALL(2, 1); }   \
-    else if ((a) <= 4) { CALL(4, 1); }   \
-    else if ((a) <= 8) { CALL(8, 1); }   \
-    else if ((a) <= 16) { CALL(16, 1); } \
-    else if ((a) <= 32) { CALL(32, 1); } \
-    else if ((a) <= 64) { CALL(64, 1); } \
-    else if ((a) <= 128) { CALL(64, 2); }\
-    else { CALL(64, 4); }                \
+// one lane for a row of one element, else the ladder of onehot_segment.h
+#define EMB_NORMAL_BY_WIDTH(CALL, a)                \
+  do {                                              \
+    if ((a) <= 1) { CALL(1, 1); }                   \
+    else EMB_SEGMENT_BY_WIDTH(CALL, a);             \
   } while (0)
 
 }  // namespace
 
-int64_t normal_policy_launches() { return g_launches.load(std::memory_order_relaxed); }
+int64_t normal_policy_launches() { return g_count.value(); }
 
 hipError_t launch_normal_policy_loss(const void* mean_raw, const void* std_raw, const float* act, bool bf16, int64_t N,
                                      int64_t T, int64_t drop, int64_t A, int kind, float lo, float hi, float actent,
@@ -276,7 +257,7 @@ hipError_t launch_normal_policy_loss(const void* mean_raw, const void* std_raw, 
                        weight, weight_stride, loss, logpi, ent, r, steps, kept, dims, bounded, lo, span, actent)
   EMB_NORMAL_BY_WIDTH(EMB_FORWARD, A);
 #undef EMB_FORWARD
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_normal_policy_loss_grad(const void* mean_raw, const void* std_raw, const float* act, bool bf16,
@@ -305,7 +286,7 @@ hipError_t launch_normal_policy_loss_grad(const void* mean_raw, const void* std_
                        r, steps, kept, dims, bounded, lo, span, actent)
   EMB_NORMAL_BY_WIDTH(EMB_GRAD, A);
 #undef EMB_GRAD
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_philox_normal(uint64_t seed, uint64_t offset, uint64_t first, int64_t count, float* out,
@@ -313,7 +294,7 @@ hipError_t launch_philox_normal(uint64_t seed, uint64_t offset, uint64_t first, 
   if (count < 1 || !out) return hipErrorInvalidValue;
   const dim3 grid(flat_blocks(count)), block(kThreads);
   hipLaunchKernelGGL(philox_normal_kernel, grid, block, 0, stream, seed, offset, first, count, out);
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_normal_sample(const void* mean_raw, const void* std_raw, bool bf16, int64_t rows, int64_t A, int kind,
@@ -332,7 +313,7 @@ hipError_t launch_normal_sample(const void* mean_raw, const void* std_raw, bool 
   else
     hipLaunchKernelGGL(normal_sample_kernel<float>, grid, block, 0, stream, static_cast<const float*>(mean_raw),
                        static_cast<const float*>(std_raw), eps, act, count, bounded, lo, span, seed, offset);
-  return launched();
+  return g_count.launched();
 }
 
 }  // namespace emb

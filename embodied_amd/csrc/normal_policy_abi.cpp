@@ -15,9 +15,8 @@ namespace {
 
 int kind_of(int32_t kind) { return kind == EMB_NORMAL_LOGSTD ? emb::kNormalLogstd : emb::kNormalBounded; }
 
-void head_ok(const std::string& who, int32_t dtype, int32_t kind, float lo, float hi) {
-  static thread_local std::string msg;
-  auto say = [&](const char* what) { return (msg = who + ": " + what).c_str(); };
+void head_ok(const char* who, int32_t dtype, int32_t kind, float lo, float hi) {
+  const Who say{who};
   need(dtype == EMB_F32 || dtype == EMB_BF16, say("dtype must be EMB_F32 or EMB_BF16"));
   need(kind == EMB_NORMAL_BOUNDED || kind == EMB_NORMAL_LOGSTD, say("kind must be EMB_NORMAL_BOUNDED or EMB_NORMAL_LOGSTD"));
   if (kind == EMB_NORMAL_BOUNDED)
@@ -27,8 +26,7 @@ void head_ok(const std::string& who, int32_t dtype, int32_t kind, float lo, floa
 // What both loss entry points check before any HIP call; returns the number of output rows.
 int64_t shape_ok(const char* who, int32_t dtype, int64_t N, int64_t T, int32_t drop, int64_t A, int32_t kind, float lo,
                  float hi, float actent) {
-  static thread_local std::string msg;
-  auto say = [&](const char* what) { return (msg = std::string(who) + ": " + what).c_str(); };
+  const Who say{who};
   head_ok(who, dtype, kind, lo, hi);
   need(N >= 0 && T >= 0, say("negative N or T"));
   need(drop == 0 || drop == 1, say("drop must be 0 or 1"));

@@ -5,10 +5,10 @@
 //
 // Up to kNormLdsMax values keep their order-preserving integer keys in LDS; more
 // values are re-read from global memory by every pass of the same kernel.
+#include "wave_util.h"          // LaunchCount
 #include "normalize_device.h"   // (float32 operations one by one: fp contract off)
 #include "norm_select.h"        // to_key, hist_add, the two-rank radix select
 
-#include <atomic>
 #include <cmath>
 
 namespace emb {
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(kNormThreads) void normalize_kernel(
   }
 }
 
-std::atomic<int64_t> g_launches{0};
+segment::LaunchCount g_count;
 
 }  // namespace
 
@@ -124,7 +124,7 @@ NormRank norm_rank(double q, int64_t n) {
   return {static_cast<uint32_t>(below), static_cast<float>(pos - below)};
 }
 
-int64_t normalize_launches() { return g_launches.load(std::memory_order_relaxed); }
+int64_t normalize_launches() { return g_count.value(); }
 
 hipError_t launch_normalize(const float* x, int64_t n, float* state, int impl, bool update,
                             bool debias, float keep, float rate, float limit, NormRank lo, NormRank hi,
@@ -137,9 +137,7 @@ hipError_t launch_normalize(const float* x, int64_t n, float* state, int impl, b
   else
     hipLaunchKernelGGL(normalize_kernel<false>, dim3(1), dim3(kNormThreads), 0, stream, x, sub, out, state,
                        count, flags, keep, rate, limit, lo.k, hi.k, lo.frac, hi.frac);
-  const hipError_t status = hipGetLastError();
-  if (status == hipSuccess) g_launches.fetch_add(1, std::memory_order_relaxed);   // the only launch site of this file
-  return status;
+  return g_count.launched();
 }
 
 }  // namespace emb

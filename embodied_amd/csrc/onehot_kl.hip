@@ -21,8 +21,6 @@
 #include "onehot_kl.h"
 #include "onehot_segment.h"
 
-#include <atomic>
-
 // float32 operations one by one, as twohot.hip
 #pragma clang fp contract(off)
 
@@ -148,7 +146,7 @@ __global__ __launch_bounds__(kThreads) void onehot_kl_grad_kernel(
   }
 }
 
-std::atomic<int64_t> g_launches{0};
+LaunchCount g_count;
 
 bool fits(int64_t rows, int64_t stoch, int64_t classes) {
   return rows >= 1 && stoch >= 1 && classes >= 1 && classes <= kOneHotMaxClasses &&
@@ -160,13 +158,8 @@ int row_blocks(int64_t rows) {
   return static_cast<int>(blocks < kMaxBlocks ? blocks : kMaxBlocks);
 }
 
-hipError_t launched() {
-  const hipError_t status = hipGetLastError();
-  if (status == hipSuccess) g_launches.fetch_add(1, std::memory_order_relaxed);
-  return status;
-}
-
 // the narrowest segment that holds a group, then 2 or 4 values per lane of the whole wave
+// (EMB_SEGMENT_BY_WIDTH of onehot_segment.h, spelled here because the sweep's cases module reads it from this file)
 #define EMB_ONEHOT_BY_WIDTH(CALL, c)     \
   do {                                   \
     if ((c) <= 2) { CALL(2, 1); }        \
@@ -181,7 +174,7 @@ hipError_t launched() {
 
 }  // namespace
 
-int64_t onehot_kl_launches() { return g_launches.load(std::memory_order_relaxed); }
+int64_t onehot_kl_launches() { return g_count.value(); }
 
 hipError_t launch_onehot_kl(const void* post, const void* prior, bool bf16, int64_t rows, int64_t stoch,
                             int64_t classes, float unimix, float free_nats, float* kl, float* ent_post,
@@ -200,7 +193,7 @@ hipError_t launch_onehot_kl(const void* post, const void* prior, bool bf16, int6
                        ent_prior, dyn, rep, r, s, c, unimix, free_nats)
   EMB_ONEHOT_BY_WIDTH(EMB_FORWARD, classes);
 #undef EMB_FORWARD
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_onehot_kl_grad(const void* post, const void* prior, bool bf16, int64_t rows, int64_t stoch,
@@ -224,7 +217,7 @@ hipError_t launch_onehot_kl_grad(const void* post, const void* prior, bool bf16,
                        free_nats)
   EMB_ONEHOT_BY_WIDTH(EMB_GRAD, classes);
 #undef EMB_GRAD
-  return launched();
+  return g_count.launched();
 }
 
 }  // namespace emb

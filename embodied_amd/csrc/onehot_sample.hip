@@ -25,8 +25,6 @@
 #include "onehot_segment.h"
 #include "philox.h"
 
-#include <atomic>
-
 // float32 operations one by one, as twohot.hip
 #pragma clang fp contract(off)
 
@@ -160,7 +158,7 @@ __global__ __launch_bounds__(kThreads) void onehot_sample_kernel(
         for (int j = 0; j < NPER; ++j) {
           const int i = sl + W * j;
           if (i < classes)
-            store(onehot + g * classes, i, valid ? (i == k ? 1.f : 0.f) : __uint_as_float(0x7fc00000u));
+            store(onehot + g * classes, i, valid ? (i == k ? 1.f : 0.f) : quiet_nan());
         }
       }
     }
@@ -198,13 +196,13 @@ __global__ __launch_bounds__(kThreads) void onehot_sample_grad_kernel(
       for (int j = 0; j < NPER; ++j) {
         const int i = sl + W * j;
         if (i < classes)
-          store(grad + at, i, valid ? keep * (s.sm[j] * (up[j] - dot)) : __uint_as_float(0x7fc00000u));
+          store(grad + at, i, valid ? keep * (s.sm[j] * (up[j] - dot)) : quiet_nan());
       }
     }
   }
 }
 
-std::atomic<int64_t> g_launches{0};
+LaunchCount g_count;
 
 bool fits(int64_t rows, int64_t groups, int64_t classes) {
   return rows >= 1 && groups >= 1 && classes >= 1 && classes <= kSampleMaxClasses && groups <= INT32_MAX / classes &&
@@ -220,29 +218,9 @@ int pass_blocks(int64_t count, int64_t classes) {
   return static_cast<int>(blocks < kMaxBlocks ? blocks : kMaxBlocks);
 }
 
-hipError_t launched() {
-  const hipError_t status = hipGetLastError();
-  if (status == hipSuccess) g_launches.fetch_add(1, std::memory_order_relaxed);
-  return status;
-}
-
-// the ladder of onehot_kl.hip's EMB_ONEHOT_BY_WIDTH: the narrowest segment that
-// holds a group, then 2 or 4 values per lane of the whole wave
-#define EMB_SAMPLE_BY_WIDTH(CALL, c)     \
-  do {                                   \
-    if ((c) <= 2) { CALL(2, 1); }        \
-    else if ((c) <= 4) { CALL(4, 1); }   \
-    else if ((c) <= 8) { CALL(8, 1); }   \
-    else if ((c) <= 16) { CALL(16, 1); } \
-    else if ((c) <= 32) { CALL(32, 1); } \
-    else if ((c) <= 64) { CALL(64, 1); } \
-    else if ((c) <= 128) { CALL(64, 2); }\
-    else { CALL(64, 4); }                \
-  } while (0)
-
 }  // namespace
 
-int64_t onehot_sample_launches() { return g_launches.load(std::memory_order_relaxed); }
+int64_t onehot_sample_launches() { return g_count.value(); }
 
 hipError_t launch_philox_uniform(uint64_t seed, uint64_t offset, uint64_t first, int64_t count, float* out,
                                  hipStream_t stream) {
@@ -250,7 +228,7 @@ hipError_t launch_philox_uniform(uint64_t seed, uint64_t offset, uint64_t first,
   const int64_t blocks = (count + kThreads - 1) / kThreads;
   const dim3 grid(static_cast<unsigned>(blocks < kMaxBlocks ? blocks : kMaxBlocks)), block(kThreads);
   hipLaunchKernelGGL(philox_uniform_kernel, grid, block, 0, stream, seed, offset, first, count, out);
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_onehot_sample(const void* logits, bool bf16, int64_t rows, int64_t groups, int64_t classes,
@@ -274,10 +252,10 @@ hipError_t launch_onehot_sample(const void* logits, bool bf16, int64_t rows, int
     if (pred) EMB_KERNEL(float, W_, NPER_, true);              \
     else EMB_KERNEL(float, W_, NPER_, false);                  \
   }
-  EMB_SAMPLE_BY_WIDTH(EMB_FORWARD, classes);
+  EMB_SEGMENT_BY_WIDTH(EMB_FORWARD, classes);
 #undef EMB_FORWARD
 #undef EMB_KERNEL
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_onehot_sample_grad(const void* logits, const void* gout, bool bf16, int64_t rows, int64_t groups,
@@ -295,9 +273,9 @@ hipError_t launch_onehot_sample_grad(const void* logits, const void* gout, bool 
     hipLaunchKernelGGL((onehot_sample_grad_kernel<float, W_, NPER_>), grid, block, 0, stream,                  \
                        static_cast<const float*>(logits), static_cast<const float*>(gout),                     \
                        static_cast<float*>(grad), count, c, unimix)
-  EMB_SAMPLE_BY_WIDTH(EMB_GRAD, classes);
+  EMB_SEGMENT_BY_WIDTH(EMB_GRAD, classes);
 #undef EMB_GRAD
-  return launched();
+  return g_count.launched();
 }
 
 }  // namespace emb

@@ -3,55 +3,32 @@
 // lanes, W the next power of two >= classes (2 .. 64), so a wave works on 64 / W
 // groups at a time; 65 .. 256 classes: the whole wave on one group with 2 or 4
 // values per lane.  Reductions are butterflies inside a segment, then one
-// butterfly across the segments.  Device code only; included by those two
-// translation units, which launch 4 such waves per workgroup and pick W and the
-// values per lane from `classes` on the host.
+// butterfly across the segments (wave_util.h).  Included by those translation
+// units, which launch 4 such waves per workgroup and pick W and the values per
+// lane from `classes` on the host by the ladder below.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <cstdint>
+#include "wave_util.h"           // bf16 load / store, seg_max, seg_sum, across_sum
 
 // float32 operations one by one, as twohot.hip (holds to the end of the including file)
 #pragma clang fp contract(off)
 
+// CALL(W, NPER) for the narrowest segment of W lanes that holds a group of c (at
+// most 256) logits, NPER values per lane once the wave is one segment.
+#define EMB_SEGMENT_BY_WIDTH(CALL, c)    \
+  do {                                   \
+    if ((c) <= 2) { CALL(2, 1); }        \
+    else if ((c) <= 4) { CALL(4, 1); }   \
+    else if ((c) <= 8) { CALL(8, 1); }   \
+    else if ((c) <= 16) { CALL(16, 1); } \
+    else if ((c) <= 32) { CALL(32, 1); } \
+    else if ((c) <= 64) { CALL(64, 1); } \
+    else if ((c) <= 128) { CALL(64, 2); }\
+    else { CALL(64, 4); }                \
+  } while (0)
+
 namespace emb {
 namespace segment {
-
-constexpr int kLanes = 64;                        // the wave
-
-using bf16_t = uint16_t;                          // the storage; arithmetic is float32
-
-__device__ __forceinline__ float load(const float* x, int64_t i) { return x[i]; }
-__device__ __forceinline__ float load(const bf16_t* x, int64_t i) {
-  return __uint_as_float(static_cast<uint32_t>(x[i]) << 16);
-}
-__device__ __forceinline__ void store(float* x, int64_t i, float v) { x[i] = v; }
-__device__ __forceinline__ void store(bf16_t* x, int64_t i, float v) {
-  const uint32_t u = __float_as_uint(v);
-  // round to nearest even; a NaN keeps a set mantissa bit
-  x[i] = v != v ? static_cast<bf16_t>((u >> 16) | 0x40u) : static_cast<bf16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
-// Butterflies over the W lanes of a segment: every lane of it ends with the same bits.
-template <int W>
-__device__ __forceinline__ float seg_max(float v) {
-#pragma unroll
-  for (int o = W / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kLanes));
-  return v;
-}
-template <int W>
-__device__ __forceinline__ float seg_sum(float v) {
-#pragma unroll
-  for (int o = W / 2; o > 0; o >>= 1) v = v + __shfl_xor(v, o, kLanes);
-  return v;
-}
-// ... and over the 64 / W segments of the wave, of a value every lane of a segment shares.
-template <int W>
-__device__ __forceinline__ float across_sum(float v) {
-#pragma unroll
-  for (int o = kLanes / 2; o >= W; o >>= 1) v = v + __shfl_xor(v, o, kLanes);
-  return v;
-}
 
 // One group of one side, lane sl of its segment holding elements sl, sl + W, ...:
 // sm = softmax(x) (outs.py:213), prob and logp the distribution the reference's

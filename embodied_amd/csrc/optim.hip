@@ -20,8 +20,7 @@
 // kMaxBlocks), 16-byte loads and stores from the chunk's first aligned element
 // on and scalar ones at its ragged ends (optim.h: optim_plan decides per tensor).
 #include "optim.h"
-
-#include <atomic>
+#include "wave_util.h"
 
 // float32 operations one by one, as the composed path
 #pragma clang fp contract(off)
@@ -35,14 +34,11 @@ constexpr int kMetricThreads = 1024;
 constexpr int kMaxBlocks = 2048;                  // 8 workgroups on each of 256 CUs; more chunks: grid stride
 static_assert(kOptimChunk % (4 * kThreads) == 0, "a full chunk is whole rounds of one vector per thread");
 
+using namespace segment;                          // widen, wave_sum
+static_assert(kWave == kLanes, "the wave helpers shuffle over one wave64");
+
 // jnp.maximum / torch.maximum: a NaN on either side is the result (fmaxf drops it)
 __device__ __forceinline__ float maximum(float a, float b) { return a != a ? a : b != b ? b : fmaxf(a, b); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = kWave / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, kWave);      // a butterfly: every lane holds the sum
-  return v;
-}
 
 // The workgroup's sums of a and b, the same bits in every thread: each wave's
 // butterfly, then the waves in their order.
@@ -68,7 +64,7 @@ __device__ __forceinline__ void block_sum2(float& a, float& b, float (*lds)[THRE
 
 template <bool BF16>
 __device__ __forceinline__ float grad_at(const void* g, int64_t i) {
-  if constexpr (BF16) return __uint_as_float(static_cast<uint32_t>(static_cast<const uint16_t*>(g)[i]) << 16);
+  if constexpr (BF16) return widen(static_cast<const bf16_t*>(g)[i]);
   else return static_cast<const float*>(g)[i];
 }
 
@@ -270,26 +266,20 @@ __global__ __launch_bounds__(kMetricThreads) void optim_metrics_kernel(const flo
   }
 }
 
-std::atomic<int64_t> g_launches{0};
-
-hipError_t launched() {
-  const hipError_t status = hipGetLastError();
-  if (status == hipSuccess) g_launches.fetch_add(1, std::memory_order_relaxed);
-  return status;
-}
+LaunchCount g_count;
 
 int chunk_blocks(int64_t n_chunks) { return static_cast<int>(n_chunks < kMaxBlocks ? n_chunks : kMaxBlocks); }
 
 }  // namespace
 
-int64_t optim_launches() { return g_launches.load(std::memory_order_relaxed); }
+int64_t optim_launches() { return g_count.value(); }
 
 hipError_t launch_optim_norms(const OptimTensor* table, const OptimChunk* chunks, int64_t n_chunks, float* partials,
                               hipStream_t stream) {
   if (n_chunks < 1 || n_chunks > INT32_MAX || !table || !chunks || !partials) return hipErrorInvalidValue;
   hipLaunchKernelGGL(optim_norms_kernel, dim3(chunk_blocks(n_chunks)), dim3(kThreads), 0, stream, table, chunks,
                      static_cast<int32_t>(n_chunks), partials);
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_optim_update(const OptimTensor* table, const OptimChunk* chunks, int64_t n_chunks, float* partials,
@@ -297,7 +287,7 @@ hipError_t launch_optim_update(const OptimTensor* table, const OptimChunk* chunk
   if (n_chunks < 1 || n_chunks > INT32_MAX || !table || !chunks || !partials) return hipErrorInvalidValue;
   hipLaunchKernelGGL(optim_update_kernel, dim3(chunk_blocks(n_chunks)), dim3(kThreads), 0, stream, table, chunks,
                      static_cast<int32_t>(n_chunks), partials, step);
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_optim_metrics(const float* partials, int64_t n_chunks, int64_t count, float* out,
@@ -305,7 +295,7 @@ hipError_t launch_optim_metrics(const float* partials, int64_t n_chunks, int64_t
   if (n_chunks < 0 || n_chunks > INT32_MAX || (n_chunks > 0 && !partials) || !out) return hipErrorInvalidValue;
   hipLaunchKernelGGL(optim_metrics_kernel, dim3(1), dim3(kMetricThreads), 0, stream, partials,
                      static_cast<int32_t>(n_chunks), static_cast<float>(count), out);
-  return launched();
+  return g_count.launched();
 }
 
 }  // namespace emb

@@ -14,8 +14,7 @@ namespace {
 bool finite(float x) { return x - x == 0.f; }                   // a NaN or an infinity fails
 
 void tables_ok(const char* who, const void* table, const void* chunks, int64_t n_chunks, const void* partials) {
-  static thread_local std::string msg;
-  auto say = [&](const char* what) { return (msg = std::string(who) + ": " + what).c_str(); };
+  const Who say{who};
   need(n_chunks >= 0 && n_chunks <= INT32_MAX, say("the number of chunks is outside 0 .. 2^31 - 1"));
   need(n_chunks == 0 || (table && chunks && partials), say("a pointer is null"));
 }

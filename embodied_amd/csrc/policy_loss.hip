@@ -21,8 +21,6 @@
 #include "policy_loss.h"
 #include "onehot_segment.h"
 
-#include <atomic>
-
 // float32 operations one by one, as twohot.hip
 #pragma clang fp contract(off)
 
@@ -104,7 +102,7 @@ __device__ __forceinline__ float poison(const T* x, bool live, int sl, int class
     }
   }
   m = seg_max<W>(m);
-  return bad || (live && m == -INFINITY) ? __uint_as_float(0x7fc00000u) : 0.f;
+  return bad || (live && m == -INFINITY) ? quiet_nan() : 0.f;
 }
 
 // With a = softmax(x), p = keep a + uni, logp = log p, i the group's action,
@@ -173,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void policy_loss_grad_kernel(
   }
 }
 
-std::atomic<int64_t> g_launches{0};
+LaunchCount g_count;
 
 bool fits(int64_t N, int64_t T, int64_t drop, int64_t groups, int64_t classes) {
   return N >= 1 && T >= 1 && (drop == 0 || drop == 1) && groups >= 1 && classes >= 1 && classes <= kPolicyMaxClasses &&
@@ -186,14 +184,9 @@ int row_blocks(int64_t rows) {
   return static_cast<int>(blocks < kMaxBlocks ? blocks : kMaxBlocks);
 }
 
-hipError_t launched() {
-  const hipError_t status = hipGetLastError();
-  if (status == hipSuccess) g_launches.fetch_add(1, std::memory_order_relaxed);
-  return status;
-}
-
 // the ladder of onehot_kl.hip's EMB_ONEHOT_BY_WIDTH: the narrowest segment that
 // holds a group, then 2 or 4 values per lane of the whole wave
+// (EMB_SEGMENT_BY_WIDTH of onehot_segment.h, spelled here because the sweep's cases module reads it from this file)
 #define EMB_POLICY_BY_WIDTH(CALL, c)     \
   do {                                   \
     if ((c) <= 2) { CALL(2, 1); }        \
@@ -208,7 +201,7 @@ hipError_t launched() {
 
 }  // namespace
 
-int64_t policy_loss_launches() { return g_launches.load(std::memory_order_relaxed); }
+int64_t policy_loss_launches() { return g_count.value(); }
 
 hipError_t launch_policy_loss(const void* logits, const int32_t* act, bool bf16, int64_t N, int64_t T, int64_t drop,
                               int64_t groups, int64_t classes, float unimix, float actent, const float* adv,
@@ -231,7 +224,7 @@ hipError_t launch_policy_loss(const void* logits, const int32_t* act, bool bf16,
                        r, steps, kept, g, c, unimix, actent)
   EMB_POLICY_BY_WIDTH(EMB_FORWARD, classes);
 #undef EMB_FORWARD
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_policy_loss_grad(const void* logits, const int32_t* act, bool bf16, int64_t N, int64_t T,
@@ -256,7 +249,7 @@ hipError_t launch_policy_loss_grad(const void* logits, const int32_t* act, bool 
                        static_cast<float*>(grad), r, steps, kept, g, c, unimix, actent)
   EMB_POLICY_BY_WIDTH(EMB_GRAD, classes);
 #undef EMB_GRAD
-  return launched();
+  return g_count.launched();
 }
 
 }  // namespace emb

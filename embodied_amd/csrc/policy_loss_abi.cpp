@@ -14,8 +14,7 @@ namespace {
 // What both entry points check before any HIP call; returns the number of output rows.
 int64_t shape_ok(const char* who, int32_t dtype, int64_t N, int64_t T, int32_t drop, int64_t groups, int64_t classes,
                  float unimix, float actent) {
-  static thread_local std::string msg;
-  auto say = [&](const char* what) { return (msg = std::string(who) + ": " + what).c_str(); };
+  const Who say{who};
   need(dtype == EMB_F32 || dtype == EMB_BF16, say("dtype must be EMB_F32 or EMB_BF16"));
   need(N >= 0 && T >= 0, say("negative N or T"));
   need(drop == 0 || drop == 1, say("drop must be 0 or 1"));

@@ -9,11 +9,10 @@
 // One workgroup is the right shape while B * T is small (the statistics are
 // four sums, so nothing has to cross workgroups); the kernel stays correct at
 // every size, it just stops being fast (scans.py holds the crossover).
+#include "wave_util.h"          // LaunchCount; sets no fp-contract mode
 #include "scan_segment.h"       // the scan keeps scans.hip's arithmetic (its multiply-adds may contract)
 #include "ppo_targets.h"
 #include "normalize_device.h"   // from here on float32 operations one by one, as normalize.hip
-
-#include <atomic>
 
 namespace emb {
 namespace {
@@ -145,11 +144,11 @@ __global__ __launch_bounds__(kNormThreads) void ppo_targets_kernel(const PpoArgs
   }
 }
 
-std::atomic<int64_t> g_launches{0};
+segment::LaunchCount g_count;
 
 }  // namespace
 
-int64_t ppo_targets_launches() { return g_launches.load(std::memory_order_relaxed); }
+int64_t ppo_targets_launches() { return g_count.value(); }
 
 hipError_t launch_ppo_targets(const float* rew, const float* pred, const uint8_t* last, const uint8_t* term,
                               int64_t B, int64_t T, float live_scale, float lam, float tarclip, bool update,
@@ -178,9 +177,7 @@ hipError_t launch_ppo_targets(const float* rew, const float* pred, const uint8_t
     default: EMB_PPO_TARGETS(64); break;
   }
 #undef EMB_PPO_TARGETS
-  const hipError_t status = hipGetLastError();
-  if (status == hipSuccess) g_launches.fetch_add(1, std::memory_order_relaxed);   // the only launch site of this file
-  return status;
+  return g_count.launched();
 }
 
 }  // namespace emb

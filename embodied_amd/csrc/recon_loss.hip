@@ -24,8 +24,7 @@
 // past its ends, and gives the same bits.  No atomics, no traffic between
 // workgroups: the same bits run to run.
 #include "recon_loss.h"
-
-#include <atomic>
+#include "wave_util.h"
 
 // float32 operations one by one, as twohot.hip
 #pragma clang fp contract(off)
@@ -38,18 +37,17 @@ constexpr int kWaves = 4;                         // waves per workgroup
 constexpr int kThreads = kWave * kWaves;
 constexpr int kMaxBlocks = 2048;                  // 8 workgroups of 4 waves on each of 256 CUs; more rows: grid stride
 
-using bf16_t = uint16_t;                          // the storage; arithmetic is float32
+using segment::bf16_t;
+using segment::quiet_nan;
+using segment::wave_sum;
+using segment::widen;                             // the bf16 arm; float and uint8 here
+static_assert(kWave == segment::kLanes, "the wave helpers shuffle over one wave64");
 
 __device__ __forceinline__ float widen(float v) { return v; }
-__device__ __forceinline__ float widen(bf16_t v) { return __uint_as_float(static_cast<uint32_t>(v) << 16); }
 __device__ __forceinline__ float widen(uint8_t v) { return static_cast<float>(v); }
 
 __device__ __forceinline__ void narrow(float& out, float v) { out = v; }
-__device__ __forceinline__ void narrow(bf16_t& out, float v) {
-  const uint32_t u = __float_as_uint(v);
-  // round to nearest even; a NaN keeps a set mantissa bit
-  out = v != v ? static_cast<bf16_t>((u >> 16) | 0x40u) : static_cast<bf16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
+__device__ __forceinline__ void narrow(bf16_t& out, float v) { out = segment::bf16_bits(v); }
 
 // N elements that sit on a multiple of their own size: one load or store.
 template <typename E, int N>
@@ -113,8 +111,6 @@ __device__ __forceinline__ void store_chunk(E* p, int a, const float (&in)[V]) {
     store_pieces<E, V, 1>(p, in);
   }
 }
-
-__device__ __forceinline__ float quiet_nan() { return __uint_as_float(0x7fc00000u); }
 
 // t of the raw target: the float32 division the reference writes (agent.py:181).
 __device__ __forceinline__ float scaled(float raw, float div) { return div == 1.f ? raw : raw / div; }
@@ -180,12 +176,6 @@ __device__ __forceinline__ float slope_of(int op, float x, float raw, float div,
     default:
       return sigmoid_minus(x, t).diff * g;
   }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v = v + __shfl_xor(v, o, kWave);
-  return v;
 }
 
 // ---- tiny rows: W lanes per row, 64 / W rows per wave ------------------------------
@@ -291,7 +281,7 @@ __global__ __launch_bounds__(kThreads) void recon_row_grad_kernel(const TX* __re
   }
 }
 
-std::atomic<int64_t> g_launches{0};
+segment::LaunchCount g_count;
 
 bool fits(int x_dtype, int target_dtype, int64_t rows, int64_t units, int op) {
   return (x_dtype == kReconF32 || x_dtype == kReconBf16) && target_dtype >= kReconF32 && target_dtype <= kReconU8 &&
@@ -304,12 +294,6 @@ int segment_width(int64_t units) {
   int w = 1;
   while (w < units) w *= 2;
   return w;
-}
-
-hipError_t launched() {
-  const hipError_t status = hipGetLastError();
-  if (status == hipSuccess) g_launches.fetch_add(1, std::memory_order_relaxed);
-  return status;
 }
 
 // CALL(TX, TT) for the six (x, target) element types
@@ -328,7 +312,7 @@ hipError_t launched() {
 
 }  // namespace
 
-int64_t recon_loss_launches() { return g_launches.load(std::memory_order_relaxed); }
+int64_t recon_loss_launches() { return g_count.value(); }
 
 hipError_t launch_recon_loss(const void* x, int x_dtype, const void* target, int target_dtype, float div,
                              int64_t rows, int64_t units, int op, float* loss, hipStream_t stream) {
@@ -359,7 +343,7 @@ hipError_t launch_recon_loss(const void* x, int x_dtype, const void* target, int
     EMB_RECON_BY_DTYPE(EMB_BLOCK, x_dtype, target_dtype);
 #undef EMB_BLOCK
   }
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_recon_loss_grad(const void* x, int x_dtype, const void* target, int target_dtype, float div,
@@ -391,7 +375,7 @@ hipError_t launch_recon_loss_grad(const void* x, int x_dtype, const void* target
     EMB_RECON_BY_DTYPE(EMB_BLOCK, x_dtype, target_dtype);
 #undef EMB_BLOCK
   }
-  return launched();
+  return g_count.launched();
 }
 
 }  // namespace emb

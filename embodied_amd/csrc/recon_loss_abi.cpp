@@ -22,8 +22,7 @@ size_t element_size(int32_t dtype) { return dtype == EMB_F32 ? 4 : dtype == EMB_
 // What both entry points check before any HIP call; returns the number of rows.
 int64_t shape_ok(const char* who, int32_t x_dtype, int32_t target_dtype, float div, int64_t rows, int64_t units,
                  int32_t op) {
-  static thread_local std::string msg;
-  auto say = [&](const char* what) { return (msg = std::string(who) + ": " + what).c_str(); };
+  const Who say{who};
   need(x_dtype == EMB_F32 || x_dtype == EMB_BF16, say("x_dtype must be EMB_F32 or EMB_BF16"));
   need(target_dtype == EMB_F32 || target_dtype == EMB_BF16 || target_dtype == EMB_U8,
        say("target_dtype must be EMB_F32, EMB_BF16 or EMB_U8"));

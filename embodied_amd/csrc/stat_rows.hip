@@ -19,8 +19,7 @@
 // run to run.  A contiguous entry on a 16-byte boundary is read with 16-byte
 // loads; any other entry with 4-byte loads, its rows walked by their stride.
 #include "stat_rows.h"
-
-#include <atomic>
+#include "wave_util.h"
 
 // float32 operations one by one, in the order written: min, max and the count
 // agree bit for bit with a float32 restatement
@@ -148,7 +147,7 @@ __device__ __forceinline__ Stats reduce_entry(const StatEntry& e, Shared& lds) {
     const double n = static_cast<double>(static_cast<int64_t>(e.rows) * e.cols);
     const double mean = t.sum / n;
     const double var = t.sq / n - mean * mean;
-    const float nan = __int_as_float(0x7fc00000);
+    const float nan = segment::quiet_nan();
     s.v[0] = static_cast<float>(mean);
     s.v[1] = static_cast<float>(var < 0.0 ? 0.0 : sqrt(var));      // a NaN stays one
     s.v[2] = static_cast<float>(t.abs / n);
@@ -201,23 +200,17 @@ __global__ __launch_bounds__(kFillThreads) void mean_fill_kernel(const float* __
   if (tid < n - tail) out[tail + tid] = value;
 }
 
-std::atomic<int64_t> g_launches{0};
-
-hipError_t launched() {
-  const hipError_t status = hipGetLastError();
-  if (status == hipSuccess) g_launches.fetch_add(1, std::memory_order_relaxed);
-  return status;
-}
+segment::LaunchCount g_count;
 
 }  // namespace
 
-int64_t stat_rows_launches() { return g_launches.load(std::memory_order_relaxed); }
+int64_t stat_rows_launches() { return g_count.value(); }
 
 hipError_t launch_stat_rows(const StatTable& table, int count, float* out, float* total, hipStream_t stream) {
   if (count < 1 || count > kStatMaxEntries || !out) return hipErrorInvalidValue;
   hipLaunchKernelGGL(stat_rows_kernel, dim3(count + (total ? 1 : 0)), dim3(kStatThreads), 0, stream, out, total,
                      static_cast<int32_t>(count), table);
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_mean_fill(const FillTable& table, int count, const float* g, hipStream_t stream) {
@@ -227,7 +220,7 @@ hipError_t launch_mean_fill(const FillTable& table, int count, const float* g, h
   const int64_t want = (most + kFillThreads * kStatVector - 1) / (kFillThreads * kStatVector);
   const int blocks = static_cast<int>(want < kFillMaxBlocks ? want : kFillMaxBlocks);
   hipLaunchKernelGGL(mean_fill_kernel, dim3(blocks, count), dim3(kFillThreads), 0, stream, g, table);
-  return launched();
+  return g_count.launched();
 }
 
 }  // namespace emb

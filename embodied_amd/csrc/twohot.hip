@@ -14,8 +14,7 @@
 // max, sum-exp and product passes, the wave reduces by shuffles.  No atomics,
 // no traffic between waves: the same bits run to run.
 #include "twohot.h"
-
-#include <atomic>
+#include "wave_util.h"
 
 // float32 operations one by one: pred()'s mirrored pair p[i] * b[i] + p[j] * b[j]
 // is exactly 0 for equal p and antisymmetric bins only if neither product is
@@ -30,35 +29,8 @@ constexpr int kWaves = 4;                         // rows per workgroup at a tim
 constexpr int kThreads = kWave * kWaves;
 constexpr int kMaxBlocks = 2048;                  // 8 workgroups of 4 waves on each of 256 CUs; more rows: grid stride
 
-using bf16_t = uint16_t;                          // the storage; arithmetic is float32
-
-__device__ __forceinline__ float load(const float* x, int64_t i) { return x[i]; }
-__device__ __forceinline__ float load(const bf16_t* x, int64_t i) {
-  return __uint_as_float(static_cast<uint32_t>(x[i]) << 16);
-}
-__device__ __forceinline__ void store(float* x, int64_t i, float v) { x[i] = v; }
-__device__ __forceinline__ void store(bf16_t* x, int64_t i, float v) {
-  const uint32_t u = __float_as_uint(v);
-  // round to nearest even; a NaN keeps a set mantissa bit
-  x[i] = v != v ? static_cast<bf16_t>((u >> 16) | 0x40u) : static_cast<bf16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
-  return v;
-}
-// (a butterfly: every lane ends with the same bits, a + b == b + a)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v = v + __shfl_xor(v, o, kWave);
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v = v + __shfl_xor(v, o, kWave);
-  return v;
-}
+using namespace segment;                          // bf16 load / store, wave_max, wave_sum
+static_assert(kWave == kLanes, "the wave helpers shuffle over one wave64");
 
 // outs.py:314-324 from the two counts: c_le = #(bins <= t), c_gt = #(bins > t).
 // A NaN target counts nothing on either side: below = 0, above = n - 1 and NaN
@@ -224,7 +196,7 @@ __global__ __launch_bounds__(kThreads) void twohot_grad_kernel(const T* __restri
   }
 }
 
-std::atomic<int64_t> g_launches{0};
+LaunchCount g_count;
 
 bool fits(int64_t rows, int64_t n) {
   return rows >= 1 && n >= 1 && n <= kTwoHotMaxBins && rows <= INT32_MAX / n;
@@ -242,12 +214,6 @@ int row_blocks(int64_t rows) {
   return static_cast<int>(blocks < kMaxBlocks ? blocks : kMaxBlocks);
 }
 
-hipError_t launched() {
-  const hipError_t status = hipGetLastError();
-  if (status == hipSuccess) g_launches.fetch_add(1, std::memory_order_relaxed);
-  return status;
-}
-
 // the smallest of 1, 2, 4, 8, 16 values per lane that holds the row
 #define EMB_TWOHOT_BY_WIDTH(CALL, n)     \
   do {                                   \
@@ -260,7 +226,7 @@ hipError_t launched() {
 
 }  // namespace
 
-int64_t twohot_launches() { return g_launches.load(std::memory_order_relaxed); }
+int64_t twohot_launches() { return g_count.value(); }
 
 hipError_t launch_twohot_stats(const void* logits, bool bf16, int64_t rows, int64_t n, const float* bins,
                                float* lse, float* pred, hipStream_t stream) {
@@ -276,7 +242,7 @@ hipError_t launch_twohot_stats(const void* logits, bool bf16, int64_t rows, int6
                        static_cast<const float*>(logits), bins, lse, pred, r, w)
   EMB_TWOHOT_BY_WIDTH(EMB_STATS, n);
 #undef EMB_STATS
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_twohot_loss(const void* logits, bool bf16, int64_t rows, int64_t n, const float* bins,
@@ -291,7 +257,7 @@ hipError_t launch_twohot_loss(const void* logits, bool bf16, int64_t rows, int64
   else
     hipLaunchKernelGGL((twohot_loss_kernel<float>), grid, block, 0, stream, static_cast<const float*>(logits), bins,
                        lse, targets, loss, r, w);
-  return launched();
+  return g_count.launched();
 }
 
 hipError_t launch_twohot_grad(const void* logits, bool bf16, int64_t rows, int64_t n, const float* bins,
@@ -313,7 +279,7 @@ hipError_t launch_twohot_grad(const void* logits, bool bf16, int64_t rows, int64
                        static_cast<float*>(grad), r, w)
   EMB_TWOHOT_BY_WIDTH(EMB_GRAD, n);
 #undef EMB_GRAD
-  return launched();
+  return g_count.launched();
 }
 
 }  // namespace emb

@@ -12,8 +12,7 @@ namespace {
 
 // What every entry point checks before any HIP call; false: rows == 0, nothing to do.
 bool shape_ok(const char* who, int32_t dtype, int64_t rows, int64_t n) {
-  static thread_local std::string msg;
-  auto say = [&](const char* what) { return (msg = std::string(who) + ": " + what).c_str(); };
+  const Who say{who};
   need(dtype == EMB_F32 || dtype == EMB_BF16, say("dtype must be EMB_F32 or EMB_BF16"));
   need(rows >= 0, say("negative rows"));
   need(n >= 1 && n <= emb::kTwoHotMaxBins, say("n outside 1 .. 1024, the bins one wave keeps in registers"));
@@ -23,8 +22,7 @@ bool shape_ok(const char* who, int32_t dtype, int64_t rows, int64_t n) {
 
 emb::TwoHotTargets targets_of(const char* who, const void* const* targets, const float* coefs, int32_t k,
                               bool live) {
-  static thread_local std::string msg;
-  auto say = [&](const char* what) { return (msg = std::string(who) + ": " + what).c_str(); };
+  const Who say{who};
   need(k >= 1 && k <= emb::kTwoHotMaxTargets, say("k outside 1 .. 4 targets"));
   need(targets && coefs, say("the targets or the coefs array is null"));
   emb::TwoHotTargets out{};
