@@ -243,6 +243,8 @@ SIGNATURES = {
     'emb_optim_table': [p, p, p, i64, p, p, i64, p, p, p],
     'emb_optim_norms': [p, p, i64, p, p],
     'emb_optim_update': [p, p, i64, p, f32, f32, f32, f32, f32, f32, f32, f32, f32, f32, f32, i32, p],
+    'emb_optim_grad_norms': [p, p, i64, p, p],
+    'emb_optim_adam_update': [p, p, i64, p, f32, f32, f32, f32, f32, f32, f32, f32, f32, f32, p],
     'emb_optim_metrics': [p, i64, i64, p, p],
     'emb_optim_launches': [p],
     'emb_norm_act': [p, p, p, i32, i64, i64, i32, i32, f32, p, p],

@@ -119,6 +119,13 @@ struct OptimStep {
   int32_t nesterov;
 };
 
+// The scalars of one update of the PPO learner's chain (ppo/agent.py:114-124:
+// clip_by_global_norm, scale_by_adam, add_decayed_weights, scale_by_learning_rate),
+// formed on the host as OptimStep's.  clip == 0: no clipping.
+struct AdamStep {
+  float lr, beta1, omb1, c1, beta2, omb2, c2, eps, clip, wd;
+};
+
 // partials is (4, n_chunks) float32: per chunk sum g^2 and sum p^2 (written by the
 // norms launch), sum upd^2 and sum p_new^2 (written by the update launch).
 // Launch 1: every chunk's sum g^2 and sum p^2 (opt.py:116-117's norms, and
@@ -130,11 +137,21 @@ hipError_t launch_optim_norms(const OptimTensor* table, const OptimChunk* chunks
 // agent.py:361-378, optax.apply_updates).
 hipError_t launch_optim_update(const OptimTensor* table, const OptimChunk* chunks, int64_t n_chunks, float* partials,
                                const OptimStep& step, hipStream_t stream);
+// Launch 1 of the Adam chain: every chunk's sum g^2 into row 0 of `partials`; the
+// parameters are not read and row 1 is not written.
+hipError_t launch_optim_grad_norms(const OptimTensor* table, const OptimChunk* chunks, int64_t n_chunks,
+                                   float* partials, hipStream_t stream);
+// Launch 2 of the Adam chain: every workgroup sums row 0 of ALL chunks in one
+// fixed order (optax.global_norm), takes the clip decision and updates its chunks
+// (optax.clip_by_global_norm, scale_by_adam, add_decayed_weights,
+// scale_by_learning_rate, apply_updates); leaves rows 2 and 3 as launch_optim_update.
+hipError_t launch_optim_adam_update(const OptimTensor* table, const OptimChunk* chunks, int64_t n_chunks,
+                                    float* partials, const AdamStep& step, hipStream_t stream);
 // out (4,) float32: grad_norm, grad_rms, update_rms, param_rms (opt.py:64, 75-78,
 // nets.py:120-124) from the partials, one workgroup, a fixed order.
 hipError_t launch_optim_metrics(const float* partials, int64_t n_chunks, int64_t count, float* out, hipStream_t stream);
 
-// Kernel launches the three launchers have issued in this process.
+// Kernel launches the five launchers have issued in this process.
 int64_t optim_launches();
 
 }  // namespace emb

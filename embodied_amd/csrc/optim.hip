@@ -16,6 +16,12 @@
 // is that synchronisation.  No atomics, no workgroup waits for another one: the
 // same bits run to run.
 //
+// The PPO learner's chain (ppo/agent.py:114-124: clip_by_global_norm,
+// scale_by_adam, add_decayed_weights, scale_by_learning_rate) runs on the same
+// tables and partials: its norms launch leaves sum g^2 only and never reads p, its
+// update launch sums the partials of ALL chunks, once per workgroup, for the one
+// global norm.
+//
 // One workgroup per chunk of kOptimChunk elements of one tensor (grid-stride past
 // kMaxBlocks), 16-byte loads and stores from the chunk's first aligned element
 // on and scalar ones at its ragged ends (optim.h: optim_plan decides per tensor).
@@ -109,31 +115,43 @@ __device__ __forceinline__ OptimTensor tensor_of(const OptimTensor* table, const
   return table[tensor];
 }
 
-template <bool BF16>
+// PARAMS: the chunk's sum p^2 as well (AGC needs it); without, p is never read
+// and psq stays as it came.
+template <bool BF16, bool PARAMS>
 __device__ __forceinline__ void norms_chunk(const OptimTensor& t, const Span& s, float& gsq, float& psq) {
   const float* p = reinterpret_cast<const float*>(t.p);
   const void* g = reinterpret_cast<const void*>(t.g);
   const int tid = threadIdx.x;
   for (int64_t i = static_cast<int64_t>(s.lo) + tid; i < s.first; i += kThreads) {
-    const float gv = grad_at<BF16>(g, i), pv = p[i];
+    const float gv = grad_at<BF16>(g, i);
     gsq = gsq + gv * gv;
-    psq = psq + pv * pv;
+    if constexpr (PARAMS) {
+      const float pv = p[i];
+      psq = psq + pv * pv;
+    }
   }
 #pragma unroll 4
   for (int32_t v = tid; v < s.nvec; v += kThreads) {
     const int32_t i = s.first + 4 * v;
     const float4 gv = grad4_at<BF16>(g, i);
-    const float4 pv = *reinterpret_cast<const float4*>(p + i);
     gsq = gsq + ((gv.x * gv.x + gv.y * gv.y) + (gv.z * gv.z + gv.w * gv.w));
-    psq = psq + ((pv.x * pv.x + pv.y * pv.y) + (pv.z * pv.z + pv.w * pv.w));
+    if constexpr (PARAMS) {
+      const float4 pv = *reinterpret_cast<const float4*>(p + i);
+      psq = psq + ((pv.x * pv.x + pv.y * pv.y) + (pv.z * pv.z + pv.w * pv.w));
+    }
   }
   for (int64_t i = static_cast<int64_t>(s.tail) + tid; i < s.hi; i += kThreads) {
-    const float gv = grad_at<BF16>(g, i), pv = p[i];
+    const float gv = grad_at<BF16>(g, i);
     gsq = gsq + gv * gv;
-    psq = psq + pv * pv;
+    if constexpr (PARAMS) {
+      const float pv = p[i];
+      psq = psq + pv * pv;
+    }
   }
 }
 
+// PARAMS = false (the Adam chain): row 0 of the partials only.
+template <bool PARAMS>
 __global__ __launch_bounds__(kThreads) void optim_norms_kernel(const OptimTensor* __restrict__ table,
                                                                const OptimChunk* __restrict__ chunks, int32_t n_chunks,
                                                                float* __restrict__ partials) {
@@ -143,12 +161,12 @@ __global__ __launch_bounds__(kThreads) void optim_norms_kernel(const OptimTensor
     const OptimTensor t = tensor_of(table, chunks, chunk, tensor, offset);
     const Span s = span_of(t, offset);
     float gsq = 0.f, psq = 0.f;
-    if (t.flags & kOptimBf16) norms_chunk<true>(t, s, gsq, psq);
-    else norms_chunk<false>(t, s, gsq, psq);
+    if (t.flags & kOptimBf16) norms_chunk<true, PARAMS>(t, s, gsq, psq);
+    else norms_chunk<false, PARAMS>(t, s, gsq, psq);
     block_sum2<kThreads>(gsq, psq, lds);
     if (threadIdx.x == 0) {
       partials[chunk] = gsq;
-      partials[static_cast<int64_t>(n_chunks) + chunk] = psq;
+      if constexpr (PARAMS) partials[static_cast<int64_t>(n_chunks) + chunk] = psq;
     }
   }
 }
@@ -243,6 +261,91 @@ __global__ __launch_bounds__(kThreads) void optim_update_kernel(const OptimTenso
   }
 }
 
+// ---- the PPO learner's chain (ppo/agent.py:114-124): clip_by_global_norm,
+// scale_by_adam, add_decayed_weights, scale_by_learning_rate, apply_updates.
+
+// One element; `clipped` and `gnorm` are the same in every thread of every
+// workgroup.  optax.clip_by_global_norm selects on gnorm < clip, so a NaN norm
+// takes the division and reaches every element of every tensor.
+__device__ __forceinline__ void adam_one(float g, float& p, float& nu, float& mu, bool clipped, float gnorm, bool decay,
+                                         const AdamStep& s, float& usq, float& pnsq) {
+  const float g1 = clipped ? (g / gnorm) * s.clip : g;             // optax.clip_by_global_norm
+  mu = s.beta1 * mu + s.omb1 * g1;                                 // optax.scale_by_adam: update_moment
+  nu = s.beta2 * nu + s.omb2 * (g1 * g1);                          //   update_moment_per_elem_norm
+  float u = (mu / s.c1) / (sqrtf(nu / s.c2) + s.eps);              //   bias_correction, eps_root = 0
+  if (decay) u = u + s.wd * p;                                     // optax.add_decayed_weights
+  const float upd = u * -s.lr;                                     // optax.scale_by_learning_rate
+  p = p + upd;                                                     // optax.apply_updates
+  usq = usq + upd * upd;
+  pnsq = pnsq + p * p;
+}
+
+template <bool BF16>
+__device__ __forceinline__ void adam_chunk(const OptimTensor& t, const Span& s, bool clipped, float gnorm,
+                                           const AdamStep& step, float& usq, float& pnsq) {
+  float* p = reinterpret_cast<float*>(t.p);
+  float* nu = reinterpret_cast<float*>(t.nu);
+  float* mu = reinterpret_cast<float*>(t.mu);
+  const void* g = reinterpret_cast<const void*>(t.g);
+  const bool decay = t.flags & kOptimDecay;
+  const int tid = threadIdx.x;
+  for (int64_t i = static_cast<int64_t>(s.lo) + tid; i < s.first; i += kThreads) {
+    float pv = p[i], nv = nu[i], mv = mu[i];
+    adam_one(grad_at<BF16>(g, i), pv, nv, mv, clipped, gnorm, decay, step, usq, pnsq);
+    p[i] = pv, nu[i] = nv, mu[i] = mv;
+  }
+#pragma unroll 2
+  for (int32_t v = tid; v < s.nvec; v += kThreads) {
+    const int32_t i = s.first + 4 * v;
+    const float4 gv = grad4_at<BF16>(g, i);
+    float4 pv = *reinterpret_cast<const float4*>(p + i);
+    float4 nv = *reinterpret_cast<const float4*>(nu + i);
+    float4 mv = *reinterpret_cast<const float4*>(mu + i);
+    adam_one(gv.x, pv.x, nv.x, mv.x, clipped, gnorm, decay, step, usq, pnsq);
+    adam_one(gv.y, pv.y, nv.y, mv.y, clipped, gnorm, decay, step, usq, pnsq);
+    adam_one(gv.z, pv.z, nv.z, mv.z, clipped, gnorm, decay, step, usq, pnsq);
+    adam_one(gv.w, pv.w, nv.w, mv.w, clipped, gnorm, decay, step, usq, pnsq);
+    *reinterpret_cast<float4*>(p + i) = pv;
+    *reinterpret_cast<float4*>(nu + i) = nv;
+    *reinterpret_cast<float4*>(mu + i) = mv;
+  }
+  for (int64_t i = static_cast<int64_t>(s.tail) + tid; i < s.hi; i += kThreads) {
+    float pv = p[i], nv = nu[i], mv = mu[i];
+    adam_one(grad_at<BF16>(g, i), pv, nv, mv, clipped, gnorm, decay, step, usq, pnsq);
+    p[i] = pv, nu[i] = nv, mu[i] = mv;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void optim_adam_update_kernel(const OptimTensor* __restrict__ table,
+                                                                     const OptimChunk* __restrict__ chunks,
+                                                                     int32_t n_chunks, float* __restrict__ partials,
+                                                                     const AdamStep step) {
+  __shared__ float lds[2][kThreads / kWave];
+  const float* gsq_of = partials;
+  float* usq_of = partials + 2 * static_cast<int64_t>(n_chunks);
+  float* pnsq_of = partials + 3 * static_cast<int64_t>(n_chunks);
+  // optax.global_norm: every chunk of every tensor, once per workgroup and in the
+  // same order in all of them, so all hold the same bits and take the same branch
+  float gsq = 0.f, unused = 0.f;
+  for (int32_t k = threadIdx.x; k < n_chunks; k += kThreads) gsq = gsq + gsq_of[k];
+  block_sum2<kThreads>(gsq, unused, lds);
+  const float gnorm = sqrtf(gsq);
+  const bool clipped = step.clip != 0.f && !(gnorm < step.clip);
+  for (int32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+    int32_t tensor, offset;
+    const OptimTensor t = tensor_of(table, chunks, chunk, tensor, offset);
+    const Span s = span_of(t, offset);
+    float usq = 0.f, pnsq = 0.f;
+    if (t.flags & kOptimBf16) adam_chunk<true>(t, s, clipped, gnorm, step, usq, pnsq);
+    else adam_chunk<false>(t, s, clipped, gnorm, step, usq, pnsq);
+    block_sum2<kThreads>(usq, pnsq, lds);
+    if (threadIdx.x == 0) {
+      usq_of[chunk] = usq;
+      pnsq_of[chunk] = pnsq;
+    }
+  }
+}
+
 __global__ __launch_bounds__(kMetricThreads) void optim_metrics_kernel(const float* __restrict__ partials,
                                                                        int32_t n_chunks, float count,
                                                                        float* __restrict__ out) {
@@ -277,8 +380,24 @@ int64_t optim_launches() { return g_count.value(); }
 hipError_t launch_optim_norms(const OptimTensor* table, const OptimChunk* chunks, int64_t n_chunks, float* partials,
                               hipStream_t stream) {
   if (n_chunks < 1 || n_chunks > INT32_MAX || !table || !chunks || !partials) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(optim_norms_kernel, dim3(chunk_blocks(n_chunks)), dim3(kThreads), 0, stream, table, chunks,
+  hipLaunchKernelGGL(optim_norms_kernel<true>, dim3(chunk_blocks(n_chunks)), dim3(kThreads), 0, stream, table, chunks,
                      static_cast<int32_t>(n_chunks), partials);
+  return g_count.launched();
+}
+
+hipError_t launch_optim_grad_norms(const OptimTensor* table, const OptimChunk* chunks, int64_t n_chunks,
+                                   float* partials, hipStream_t stream) {
+  if (n_chunks < 1 || n_chunks > INT32_MAX || !table || !chunks || !partials) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(optim_norms_kernel<false>, dim3(chunk_blocks(n_chunks)), dim3(kThreads), 0, stream, table, chunks,
+                     static_cast<int32_t>(n_chunks), partials);
+  return g_count.launched();
+}
+
+hipError_t launch_optim_adam_update(const OptimTensor* table, const OptimChunk* chunks, int64_t n_chunks,
+                                    float* partials, const AdamStep& step, hipStream_t stream) {
+  if (n_chunks < 1 || n_chunks > INT32_MAX || !table || !chunks || !partials) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(optim_adam_update_kernel, dim3(chunk_blocks(n_chunks)), dim3(kThreads), 0, stream, table, chunks,
+                     static_cast<int32_t>(n_chunks), partials, step);
   return g_count.launched();
 }
 

@@ -1,6 +1,8 @@
 // emb_optim_*: the reference's optimizer chain (embodied/jax/opt.py:109-164 under
 // dreamerv3/agent.py:342-379) over every parameter tensor in two kernel launches,
-// its metrics (opt.py:64-79) in a third one when asked (optim.hip).  Its own
+// its metrics (opt.py:64-79) in a third one when asked (optim.hip); and the PPO
+// learner's chain (ppo/agent.py:114-124) on the same tables, emb_optim_grad_norms
+// and emb_optim_adam_update.  Its own
 // translation unit, as policy_loss_abi.cpp: kernels_abi.cpp is also linked into
 // the host sanitizer soak, against stand-in launchers that know nothing of these
 // kernels.
@@ -63,6 +65,35 @@ int32_t emb_optim_update(const void* table, const void* chunks, int64_t n_chunks
     HIP_OK(emb::launch_optim_update(static_cast<const emb::OptimTensor*>(table),
                                     static_cast<const emb::OptimChunk*>(chunks), n_chunks,
                                     static_cast<float*>(partials), step, static_cast<hipStream_t>(stream)));
+  });
+}
+
+int32_t emb_optim_grad_norms(const void* table, const void* chunks, int64_t n_chunks, void* partials, void* stream) {
+  return guarded([&] {
+    need(n_chunks >= 1 && n_chunks <= INT32_MAX, "optim_grad_norms: the number of chunks is outside 1 .. 2^31 - 1");
+    need(table && chunks && partials, "optim_grad_norms: a pointer is null");
+    HIP_OK(emb::launch_optim_grad_norms(static_cast<const emb::OptimTensor*>(table),
+                                        static_cast<const emb::OptimChunk*>(chunks), n_chunks,
+                                        static_cast<float*>(partials), static_cast<hipStream_t>(stream)));
+  });
+}
+
+int32_t emb_optim_adam_update(const void* table, const void* chunks, int64_t n_chunks, void* partials, float lr,
+                              float beta1, float omb1, float c1, float beta2, float omb2, float c2, float eps,
+                              float clip, float wd, void* stream) {
+  return guarded([&] {
+    need(n_chunks >= 1 && n_chunks <= INT32_MAX, "optim_adam_update: the number of chunks is outside 1 .. 2^31 - 1");
+    need(table && chunks && partials, "optim_adam_update: a pointer is null");
+    need(finite(lr), "optim_adam_update: lr must be finite");
+    need(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "optim_adam_update: a beta outside [0, 1)");
+    need(omb1 > 0.f && omb1 <= 1.f && omb2 > 0.f && omb2 <= 1.f, "optim_adam_update: 1 - beta outside (0, 1]");
+    need(c1 > 0.f && c1 <= 1.f && c2 > 0.f && c2 <= 1.f, "optim_adam_update: a bias correction outside (0, 1]");
+    need(eps >= 0.f && finite(eps) && clip >= 0.f && finite(clip) && wd >= 0.f && finite(wd),
+         "optim_adam_update: eps, clip and wd must be finite and not negative");
+    const emb::AdamStep step{lr, beta1, omb1, c1, beta2, omb2, c2, eps, clip, wd};
+    HIP_OK(emb::launch_optim_adam_update(static_cast<const emb::OptimTensor*>(table),
+                                         static_cast<const emb::OptimChunk*>(chunks), n_chunks,
+                                         static_cast<float*>(partials), step, static_cast<hipStream_t>(stream)));
   });
 }
 

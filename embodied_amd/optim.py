@@ -1,11 +1,11 @@
-"""The reference learners' optimizer (embodied/jax/opt.py:109-164 chained by
-dreamerv3/agent.py:342-379) as a `torch.optim.Optimizer` over CUDA tensors:
-adaptive gradient clipping per tensor, RMS scaling, bias-corrected momentum,
-optional weight decay and a learning-rate schedule, in two HIP launches per
-`step()` whatever the number of parameter tensors.
+"""The reference learners' optimizers as `torch.optim.Optimizer`s over CUDA
+tensors, each in two HIP launches per `step()` whatever the number of parameter
+tensors.
 
-Per tensor, in float32, `t` the number of this update counted from 1 (`eps` is
-not inside the root):
+`LaProp`: embodied/jax/opt.py:109-164 chained by dreamerv3/agent.py:342-379:
+adaptive gradient clipping per tensor, RMS scaling, bias-corrected momentum,
+optional weight decay and a learning-rate schedule.  Per tensor, in float32, `t`
+the number of this update counted from 1 (`eps` is not inside the root):
 
     unorm = ||g||2 ; pnorm = ||p||2                                   opt.py:116-117
     g1    = g * (1 / maximum(1, unorm / (agc * maximum(pmin, pnorm))))    agc == 0: g
@@ -23,8 +23,27 @@ the finite elements go on with g1 = 0 and the infinite ones become NaN.  No othe
 tensor is touched.  There is no loss scaling and no skipped step (opt.py:25-29
 belongs to float16 compute).
 
-Two paths, as the heads in `outs.py`: the composed one restates the reference
-line by line in torch ops and is the definition; the fused one is csrc/optim.hip.
+`Adam`: the PPO learner's chain, ppo/agent.py:114-124: optax.clip_by_global_norm,
+scale_by_adam, add_decayed_weights, scale_by_learning_rate.  In float32, `t` as
+above, count = t - 1:
+
+    gnorm = sqrt(sum over EVERY tensor of sum g^2)                    optax.global_norm
+    g1    = g  if clip == 0 or gnorm < clip  else  (g / gnorm) * clip    clip_by_global_norm
+    mu    = beta1 * mu + (1 - beta1) * g1
+    nu    = beta2 * nu + (1 - beta2) * (g1 * g1)
+    u     = (mu / (1 - beta1**t)) / (sqrt(nu / (1 - beta2**t)) + eps)  scale_by_adam, eps_root = 0
+    u     = u + wd * p  if the tensor decays                          add_decayed_weights
+    upd   = u * -lr(count) ;  p = p + upd
+
+The clip is a select on `gnorm < clip`, not a `min`, and the norm is one number
+for all tensors.  So, on purpose unlike LaProp's per-tensor containment and as the
+reference behaves: a NaN in ANY gradient makes p, mu and nu NaN in EVERY tensor;
+an infinity and no NaN gives g / inf * clip, 0 for the finite elements of every
+tensor and NaN for the infinite ones.  gnorm == 0 leaves the gradients alone.
+
+Two paths each, as the heads in `outs.py`: the composed one restates the
+reference line by line in torch ops and is the definition; the fused one is
+csrc/optim.hip.
 """
 import ctypes as C
 
@@ -49,24 +68,18 @@ CHUNK, RECORD_BYTES = _geometry()
 BF16, DECAY = 1, 2                  # EMB_OPTIM_BF16, EMB_OPTIM_DECAY
 _GRADS = {torch.float32: 0, torch.bfloat16: BF16}
 
-# `fused=None`: the kernels wherever they fit.  On the MI355X the fused median is
-# below the composed one at all six rows of profiles/optim_bench.txt -- 1 M
-# parameters in 40 tensors 72.2 us against 6572.8 (bf16 gradients 74.8 / 6917.9),
-# the 12.2 M PPO model 81.8 / 7532.0 (80.4 / 7750.6), the 166 M DreamerV3 model
-# 1050.5 / 15853.6 (941.7 / 17519.4) -- so there is no size below which the
-# composed path is taken and no crossover constant here.
-
 
 def optimizer_launches():
-  """Kernel launches `emb_optim_norms`, `emb_optim_update` and `emb_optim_metrics`
-  have issued in this process."""
+  """Kernel launches `emb_optim_norms`, `emb_optim_update`, `emb_optim_grad_norms`,
+  `emb_optim_adam_update` and `emb_optim_metrics` have issued in this process."""
   return _lib.launches('optim')
 
 
 def warmup_schedule(lr, warmup):
   """`count -> lr * min(count / warmup, 1)`: the reference's default schedule,
   join_schedules([linear_schedule(0, lr, warmup), constant_schedule(lr)],
-  [warmup]) of agent.py:367-378.  warmup == 0: the constant."""
+  [warmup]) of agent.py:367-378, and optax.linear_schedule(0, lr, warmup) of
+  ppo/agent.py:118, which is the same function.  warmup == 0: the constant."""
   lr, warmup = float(lr), int(warmup)
   if not warmup:
     return lambda count: lr
@@ -74,17 +87,50 @@ def warmup_schedule(lr, warmup):
 
 
 def _check_param(index, param):
-  """A parameter the optimizer takes: a CUDA float32 tensor."""
+  """A parameter the optimizers take: a CUDA float32 tensor."""
   if not torch.is_tensor(param):
-    raise TypeError(f'LaProp: parameter {index} is a {type(param).__name__}, not a tensor')
+    raise TypeError(f'embodied_amd.optim: parameter {index} is a {type(param).__name__}, not a tensor')
   if param.dtype != torch.float32:
-    raise TypeError(f'LaProp: parameter {index} must be float32, got {param.dtype} (no CPU fallback, no other dtype)')
+    raise TypeError(f'embodied_amd.optim: parameter {index} must be float32, got {param.dtype} '
+                    '(no CPU fallback, no other dtype)')
   if not param.is_cuda:
     raise RuntimeError(f'embodied_amd.optim runs as HIP kernels: parameter {index} is not a CUDA tensor '
                        '(no CPU fallback)')
 
 
-def _path(fused, params):
+def _check_hyper(who, betas, amounts, lr, warmup):
+  """The checks both optimizers make before they touch a parameter.  Returns the
+  schedule: the callable `lr`, or None for a float."""
+  for name, value in betas.items():
+    if not 0.0 <= value < 1.0:
+      raise ValueError(f'{who}: {name} = {value!r} is outside [0, 1)')
+  for name, value in amounts.items():
+    if not (value >= 0.0 and np.isfinite(value)):
+      raise ValueError(f'{who}: {name} = {value!r} must be finite and not negative')
+  if int(warmup) != warmup or warmup < 0:
+    raise ValueError(f'{who}: warmup = {warmup!r} must be a whole number of updates, 0 or more')
+  if callable(lr):
+    if warmup:
+      raise ValueError(f'{who}: warmup goes with a float lr; a callable lr is the whole schedule')
+    return lr
+  if not np.isfinite(lr):
+    raise ValueError(f'{who}: lr = {lr!r} must be finite')
+  return None
+
+
+# `fused=None`: the kernels wherever they fit.  On the MI355X the fused median is
+# below the composed one at all six rows of profiles/optim_bench.txt -- 1 M
+# parameters in 40 tensors 72.2 us against 6572.8 (bf16 gradients 74.8 / 6917.9),
+# the 12.2 M PPO model 81.8 / 7532.0 (80.4 / 7750.6), the 166 M DreamerV3 model
+# 1050.5 / 15853.6 (941.7 / 17519.4) -- so there is no size below which the
+# composed path is taken and no crossover constant here.
+# The same holds for `Adam` at all six rows of profiles/adam_bench.txt -- 1 M
+# parameters in 40 tensors 73.0 us against 5510.8 (bf16 gradients 73.5 / 5181.9),
+# the 12.2 M PPO model 78.8 / 5847.2 (78.6 / 5326.5), the 166 M model 1005.1 /
+# 11384.1 (866.9 / 11645.8) -- so `Adam` has no crossover constant either.
+
+
+def _path(fused, params, who='LaProp'):
   """True: the kernels, False: the composed path.  The kernels take contiguous
   tensors of fewer than 2^31 elements each; one that is not puts the whole
   optimizer on the composed path (fused=None) or is refused (fused=True)."""
@@ -97,7 +143,7 @@ def _path(fused, params):
     if why:
       break
   if fused and why:
-    raise ValueError(f'LaProp(fused=True): {why} (fused=None or False composes it)')
+    raise ValueError(f'{who}(fused=True): {why} (fused=None or False composes it)')
   if fused is None:
     return why is None
   return bool(fused)
@@ -112,64 +158,33 @@ def _moment_like(param):
   return flat[offset:].view(param.shape)
 
 
-class LaProp(torch.optim.Optimizer):
-  """`LaProp(params, lr=4e-5, agc=0.3, pmin=1e-3, eps=1e-20, beta1=0.9,
-  beta2=0.999, nesterov=False, wd=0.0, wd_mask=None, warmup=0, fused=None)`
+class _TableOptimizer(torch.optim.Optimizer):
+  """What `LaProp` and `Adam` share: one parameter group of CUDA float32 tensors,
+  the float32 moments `nu` and `mu` in `state[p]`, the update count in
+  `param_groups[0]['updates']`, the schedule, the checks of a step's gradients,
+  the device table of csrc/optim.h with its uploads, and the metrics.  A
+  subclass has `_composed_step` and `_fused_step`."""
 
-  params    an iterable of CUDA float32 tensors, one parameter group
-  lr        a float, or a callable `count -> float` evaluated on the host with
-            count = the number of updates applied so far (the first sees 0, as
-            optax.scale_by_schedule)
-  warmup    with a float lr: lr * min(count / warmup, 1), so the very first update
-            has step size 0 (agent.py:375-377); anneals go through the callable
-  wd_mask   one bool per parameter; None decays tensors with dim() >= 2, the
-            torch-side counterpart of the reference's r'/kernel$' (agent.py:352)
-  fused     None: the kernels where they fit; True / False force a path, True
-            raises where they do not fit and says why
-
-  Gradients are float32 or bfloat16, widened to float32 in registers; the
-  moments are float32 and live in `state[p]['nu']`, `state[p]['mu']`; the update
-  count is `param_groups[0]['updates']`, so `state_dict` carries all of it.
-  """
-
-  def __init__(self, params, lr=4e-5, agc=0.3, pmin=1e-3, eps=1e-20, beta1=0.9, beta2=0.999, nesterov=False, wd=0.0,
-               wd_mask=None, warmup=0, fused=None):
-    for name, value in (('beta1', beta1), ('beta2', beta2)):
-      if not 0.0 <= value < 1.0:
-        raise ValueError(f'LaProp: {name} = {value!r} is outside [0, 1)')
-    for name, value in (('agc', agc), ('pmin', pmin), ('eps', eps), ('wd', wd)):
-      if not (value >= 0.0 and np.isfinite(value)):
-        raise ValueError(f'LaProp: {name} = {value!r} must be finite and not negative')
-    if int(warmup) != warmup or warmup < 0:
-      raise ValueError(f'LaProp: warmup = {warmup!r} must be a whole number of updates, 0 or more')
-    if callable(lr):
-      if warmup:
-        raise ValueError('LaProp: warmup goes with a float lr; a callable lr is the whole schedule')
-      self._schedule = lr
-    else:
-      if not np.isfinite(lr):
-        raise ValueError(f'LaProp: lr = {lr!r} must be finite')
-      self._schedule = None
-    defaults = dict(lr=None if callable(lr) else float(lr), agc=float(agc), pmin=float(pmin), eps=float(eps),
-                    beta1=float(beta1), beta2=float(beta2), nesterov=bool(nesterov), wd=float(wd), warmup=int(warmup),
-                    updates=0)
+  def _setup(self, params, defaults, schedule, wd_mask, fused, moments):
+    who = type(self).__name__
+    self._schedule = schedule
     params = list(params)
     if any(isinstance(entry, dict) for entry in params):
-      raise ValueError('LaProp: one parameter group; pass the tensors themselves')
+      raise ValueError(f'{who}: one parameter group; pass the tensors themselves')
     for index, param in enumerate(params):
       _check_param(index, param)
-    super().__init__(params, defaults)
+    torch.optim.Optimizer.__init__(self, params, defaults)
     group = self.param_groups[0]['params']
     if wd_mask is None:
       wd_mask = [param.dim() >= 2 for param in group]
     wd_mask = [bool(flag) for flag in wd_mask]
     if len(wd_mask) != len(group):
-      raise ValueError(f'LaProp: wd_mask has {len(wd_mask)} entries for {len(group)} parameters')
+      raise ValueError(f'{who}: wd_mask has {len(wd_mask)} entries for {len(group)} parameters')
     self.wd_mask = tuple(wd_mask)
-    self.fused = _path(fused, group)
+    self.fused = _path(fused, group, who)
     self.param_count = sum(param.numel() for param in group)
     for param in group:
-      self.state[param] = {'nu': _moment_like(param), 'mu': _moment_like(param)}
+      self.state[param] = {name: _moment_like(param) for name in moments}
     self._plan = None               # the device tables, made by the first fused step
     self._sums = None               # the composed path's sums of squares of the last step
     self.table_uploads = 0          # how often the device table was (re)written
@@ -189,16 +204,17 @@ class LaProp(torch.optim.Optimizer):
     return group, lr, 1 - group['beta1'] ** t, 1 - group['beta2'] ** t
 
   def _gradients(self, group):
+    who = type(self).__name__
     grads = []
     for index, param in enumerate(group['params']):
       grad = param.grad
       if grad is None:
-        raise ValueError(f'LaProp.step: parameter {index} has no gradient (the reference has one for every leaf, '
-                         'and AGC of a missing tensor has no definition)')
+        raise ValueError(f'{who}.step: parameter {index} has no gradient (the reference has one for every leaf, '
+                         'and the norm of a missing tensor has no definition)')
       if grad.dtype not in _GRADS:
-        raise TypeError(f'LaProp.step: the gradient of parameter {index} must be float32 or bfloat16, got {grad.dtype}')
+        raise TypeError(f'{who}.step: the gradient of parameter {index} must be float32 or bfloat16, got {grad.dtype}')
       if grad.shape != param.shape or grad.device != param.device:
-        raise ValueError(f'LaProp.step: the gradient of parameter {index} is {tuple(grad.shape)} on {grad.device}, '
+        raise ValueError(f'{who}.step: the gradient of parameter {index} is {tuple(grad.shape)} on {grad.device}, '
                          f'the parameter {tuple(param.shape)} on {param.device}')
       grads.append(grad)
     return grads
@@ -214,7 +230,7 @@ class LaProp(torch.optim.Optimizer):
     moments = [self.state[param] for param in group['params']]
     why = self._misfit(group['params'], grads, moments) if self.fused else 'composed'
     if self.fused and why:
-      raise ValueError(f'LaProp.step (fused): {why}')
+      raise ValueError(f'{type(self).__name__}.step (fused): {why}')
     if self.fused:
       self._fused_step(group, grads, moments, lr, c1, c2)
     else:
@@ -230,7 +246,7 @@ class LaProp(torch.optim.Optimizer):
     after the update), Python ints `updates` and `param_count`.  No host
     synchronisation; on the fused path one launch, issued here and only here."""
     if not self._stepped:
-      raise RuntimeError('LaProp.metrics: no step yet')
+      raise RuntimeError(f'{type(self).__name__}.metrics: no step yet')
     if self.fused:
       plan = self._plan
       out = _lib.empty((4,), torch.float32, plan['device'])
@@ -244,35 +260,6 @@ class LaProp(torch.optim.Optimizer):
       grad_rms, update_rms, param_rms = (torch.sqrt(x / count) for x in (gsq, usq, psq))    # nets.py:123-124
     return {'grad_norm': grad_norm, 'grad_rms': grad_rms, 'update_rms': update_rms, 'param_rms': param_rms,
             'updates': self.param_groups[0]['updates'], 'param_count': self.param_count}
-
-  # ---------------------------------------------------------------- the composed path
-
-  def _composed_step(self, group, grads, moments, lr, c1, c2):
-    """The reference's chain restated line by line; the definition."""
-    agc, pmin, eps, wd = group['agc'], group['pmin'], group['eps'], group['wd']
-    beta1, beta2, nesterov = group['beta1'], group['beta2'], group['nesterov']
-    gsq, usq, psq = [], [], []
-    for param, grad, state, decays in zip(group['params'], grads, moments, self.wd_mask):
-      nu, mu = state['nu'], state['mu']
-      g = grad.to(torch.float32)
-      gsq.append(torch.square(g).sum())
-      if agc:                                                              # opt.py:120
-        unorm = torch.sqrt(gsq[-1])                                        # opt.py:116, as jnp.linalg.norm does it:
-        pnorm = torch.sqrt(torch.square(param).sum())                      # opt.py:117  sqrt(sum(x * x))
-        upper = agc * torch.maximum(torch.full_like(pnorm, pmin), pnorm)   # opt.py:118
-        g = g * (1 / torch.maximum(torch.ones_like(unorm), unorm / upper))  # opt.py:119
-      nu.copy_(beta2 * nu + (1 - beta2) * (g * g))                         # opt.py:136-137
-      u = g / (torch.sqrt(nu / c2) + eps)                                  # opt.py:138-140, optax.bias_correction
-      mu.copy_((1 - beta1) * u + beta1 * mu)                               # opt.py:156, optax.update_moment
-      m = (1 - beta1) * u + beta1 * mu if nesterov else mu                 # opt.py:157-161
-      m = m / c1
-      if wd and decays:                                                    # agent.py:361-365
-        m = m + wd * param
-      upd = m * -lr                                                        # agent.py:378, scale_by_learning_rate
-      param.add_(upd)                                                      # opt.py:62, optax.apply_updates
-      usq.append(torch.square(upd).sum())
-      psq.append(torch.square(param).sum())
-    self._sums = tuple(torch.stack(x).sum() for x in (gsq, usq, psq))      # nets.py:123
 
   # ------------------------------------------------------------------- the fused path
 
@@ -328,7 +315,9 @@ class LaProp(torch.optim.Optimizer):
     plan['addrs'], plan['flags'] = addrs, flags
     self.table_uploads += 1
 
-  def _fused_step(self, group, grads, moments, lr, c1, c2):
+  def _tables(self, group, grads, moments):
+    """The plan with the table of this step's addresses on the device, uploaded
+    only where one differs from the last step's."""
     params = group['params']
     wd = group['wd']
     addrs, flags = [], []
@@ -339,6 +328,67 @@ class LaProp(torch.optim.Optimizer):
     if plan is None or plan['addrs'] != addrs or plan['flags'] != flags:
       self._refresh(params, addrs, flags)
       plan = self._plan
+    return plan
+
+
+class LaProp(_TableOptimizer):
+  """`LaProp(params, lr=4e-5, agc=0.3, pmin=1e-3, eps=1e-20, beta1=0.9,
+  beta2=0.999, nesterov=False, wd=0.0, wd_mask=None, warmup=0, fused=None)`
+
+  params    an iterable of CUDA float32 tensors, one parameter group
+  lr        a float, or a callable `count -> float` evaluated on the host with
+            count = the number of updates applied so far (the first sees 0, as
+            optax.scale_by_schedule)
+  warmup    with a float lr: lr * min(count / warmup, 1), so the very first update
+            has step size 0 (agent.py:375-377); anneals go through the callable
+  wd_mask   one bool per parameter; None decays tensors with dim() >= 2, the
+            torch-side counterpart of the reference's r'/kernel$' (agent.py:352)
+  fused     None: the kernels where they fit; True / False force a path, True
+            raises where they do not fit and says why
+
+  Gradients are float32 or bfloat16, widened to float32 in registers; the
+  moments are float32 and live in `state[p]['nu']`, `state[p]['mu']`; the update
+  count is `param_groups[0]['updates']`, so `state_dict` carries all of it.
+  """
+
+  def __init__(self, params, lr=4e-5, agc=0.3, pmin=1e-3, eps=1e-20, beta1=0.9, beta2=0.999, nesterov=False, wd=0.0,
+               wd_mask=None, warmup=0, fused=None):
+    schedule = _check_hyper('LaProp', dict(beta1=beta1, beta2=beta2), dict(agc=agc, pmin=pmin, eps=eps, wd=wd), lr,
+                            warmup)
+    defaults = dict(lr=None if callable(lr) else float(lr), agc=float(agc), pmin=float(pmin), eps=float(eps),
+                    beta1=float(beta1), beta2=float(beta2), nesterov=bool(nesterov), wd=float(wd), warmup=int(warmup),
+                    updates=0)
+    self._setup(params, defaults, schedule, wd_mask, fused, ('nu', 'mu'))
+
+  def _composed_step(self, group, grads, moments, lr, c1, c2):
+    """The reference's chain restated line by line; the definition."""
+    agc, pmin, eps, wd = group['agc'], group['pmin'], group['eps'], group['wd']
+    beta1, beta2, nesterov = group['beta1'], group['beta2'], group['nesterov']
+    gsq, usq, psq = [], [], []
+    for param, grad, state, decays in zip(group['params'], grads, moments, self.wd_mask):
+      nu, mu = state['nu'], state['mu']
+      g = grad.to(torch.float32)
+      gsq.append(torch.square(g).sum())
+      if agc:                                                              # opt.py:120
+        unorm = torch.sqrt(gsq[-1])                                        # opt.py:116, as jnp.linalg.norm does it:
+        pnorm = torch.sqrt(torch.square(param).sum())                      # opt.py:117  sqrt(sum(x * x))
+        upper = agc * torch.maximum(torch.full_like(pnorm, pmin), pnorm)   # opt.py:118
+        g = g * (1 / torch.maximum(torch.ones_like(unorm), unorm / upper))  # opt.py:119
+      nu.copy_(beta2 * nu + (1 - beta2) * (g * g))                         # opt.py:136-137
+      u = g / (torch.sqrt(nu / c2) + eps)                                  # opt.py:138-140, optax.bias_correction
+      mu.copy_((1 - beta1) * u + beta1 * mu)                               # opt.py:156, optax.update_moment
+      m = (1 - beta1) * u + beta1 * mu if nesterov else mu                 # opt.py:157-161
+      m = m / c1
+      if wd and decays:                                                    # agent.py:361-365
+        m = m + wd * param
+      upd = m * -lr                                                        # agent.py:378, scale_by_learning_rate
+      param.add_(upd)                                                      # opt.py:62, optax.apply_updates
+      usq.append(torch.square(upd).sum())
+      psq.append(torch.square(param).sum())
+    self._sums = tuple(torch.stack(x).sum() for x in (gsq, usq, psq))      # nets.py:123
+
+  def _fused_step(self, group, grads, moments, lr, c1, c2):
+    plan = self._tables(group, grads, moments)
     if not plan['n_chunks']:
       return
     stream = _lib.raw_stream(plan['device'])
@@ -346,4 +396,77 @@ class LaProp(torch.optim.Optimizer):
     beta1, beta2 = group['beta1'], group['beta2']
     api.emb_optim_norms(table, chunks, plan['n_chunks'], partials, stream)
     api.emb_optim_update(table, chunks, plan['n_chunks'], partials, lr, beta1, 1 - beta1, c1, beta2, 1 - beta2, c2,
-                         group['eps'], group['agc'], group['pmin'], wd, int(group['nesterov']), stream)
+                         group['eps'], group['agc'], group['pmin'], group['wd'], int(group['nesterov']), stream)
+
+
+class Adam(_TableOptimizer):
+  """`Adam(params, lr=3e-4, clip=10.0, eps=1e-7, beta1=0.9, beta2=0.999, wd=0.0,
+  wd_mask=None, warmup=1000, fused=None)`: the PPO learner's optimizer
+  (ppo/agent.py:114-124 with the defaults of ppo/configs.yaml:101), in place of
+  `nn.utils.clip_grad_norm_` followed by `torch.optim.Adam`.
+
+  params    an iterable of CUDA float32 tensors, one parameter group
+  lr        a float, or a callable `count -> float` evaluated on the host with
+            count = the number of updates applied so far (the first sees 0); a
+            callable is the whole schedule and goes with warmup=0
+  clip      the bound on the global norm of all gradients; 0 switches it off
+  warmup    with a float lr: lr * min(count / warmup, 1), optax.linear_schedule(0,
+            lr, warmup): the very first update has step size 0
+  wd_mask   one bool per parameter; None decays tensors with dim() >= 2, the
+            torch-side counterpart of the reference's r'/kernel$'
+  fused     None: the kernels where they fit; True / False force a path, True
+            raises where they do not fit and says why
+
+  The clip decision is one for all tensors, and it is a select on `gnorm < clip`:
+  a NaN in any gradient makes p, mu and nu NaN in EVERY tensor, an infinity and
+  no NaN gives g1 = 0 at the finite elements of every tensor and NaN at the
+  infinite ones.  That is the reference's behaviour and differs on purpose from
+  `LaProp`, whose clipping and whose NaN stay inside one tensor.
+
+  Gradients are float32 or bfloat16, widened to float32 in registers; the
+  moments are float32 and live in `state[p]['mu']`, `state[p]['nu']`; the update
+  count is `param_groups[0]['updates']`, so `state_dict` carries all of it.
+  `metrics()` is `LaProp.metrics()`: `grad_norm` is the norm of the raw gradients.
+  """
+
+  def __init__(self, params, lr=3e-4, clip=10.0, eps=1e-7, beta1=0.9, beta2=0.999, wd=0.0, wd_mask=None, warmup=1000,
+               fused=None):
+    schedule = _check_hyper('Adam', dict(beta1=beta1, beta2=beta2), dict(clip=clip, eps=eps, wd=wd), lr, warmup)
+    defaults = dict(lr=None if callable(lr) else float(lr), clip=float(clip), eps=float(eps), beta1=float(beta1),
+                    beta2=float(beta2), wd=float(wd), warmup=int(warmup), updates=0)
+    self._setup(params, defaults, schedule, wd_mask, fused, ('mu', 'nu'))
+
+  def _composed_step(self, group, grads, moments, lr, c1, c2):
+    """The reference's chain restated line by line; the definition."""
+    clip, eps, wd = group['clip'], group['eps'], group['wd']
+    beta1, beta2 = group['beta1'], group['beta2']
+    gs = [grad.to(torch.float32) for grad in grads]
+    gsq = torch.stack([torch.square(g).sum() for g in gs]).sum()
+    if clip:                                                               # optax.clip_by_global_norm
+      gnorm = torch.sqrt(gsq)                                              # optax.global_norm
+      trigger = gnorm < clip
+      gs = [torch.where(trigger, g, (g / gnorm) * clip) for g in gs]
+    usq, psq = [], []
+    for param, g, state, decays in zip(group['params'], gs, moments, self.wd_mask):
+      mu, nu = state['mu'], state['nu']
+      mu.copy_(beta1 * mu + (1 - beta1) * g)                               # optax.scale_by_adam: update_moment
+      nu.copy_(beta2 * nu + (1 - beta2) * (g * g))                         #   update_moment_per_elem_norm
+      u = (mu / c1) / (torch.sqrt(nu / c2) + eps)                          #   bias_correction, eps_root = 0
+      if wd and decays:                                                    # optax.add_decayed_weights
+        u = u + wd * param
+      upd = u * -lr                                                        # optax.scale_by_learning_rate
+      param.add_(upd)                                                      # optax.apply_updates
+      usq.append(torch.square(upd).sum())
+      psq.append(torch.square(param).sum())
+    self._sums = (gsq, torch.stack(usq).sum(), torch.stack(psq).sum())
+
+  def _fused_step(self, group, grads, moments, lr, c1, c2):
+    plan = self._tables(group, grads, moments)
+    if not plan['n_chunks']:
+      return
+    stream = _lib.raw_stream(plan['device'])
+    table, chunks, partials = plan['table'].data_ptr(), plan['chunks'].data_ptr(), plan['partials'].data_ptr()
+    beta1, beta2 = group['beta1'], group['beta2']
+    api.emb_optim_grad_norms(table, chunks, plan['n_chunks'], partials, stream)
+    api.emb_optim_adam_update(table, chunks, plan['n_chunks'], partials, lr, beta1, 1 - beta1, c1, beta2, 1 - beta2, c2,
+                              group['eps'], group['clip'], group['wd'], stream)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports (155 functions). */
+ * it exports (157 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -52,8 +52,9 @@ extern "C" {
  * emb_onehot_sample_launches, emb_recon_loss, emb_recon_loss_grad,
  * emb_recon_loss_launches, emb_normal_policy_loss, emb_normal_policy_loss_grad,
  * emb_normal_sample, emb_philox_normal, emb_normal_policy_launches,
- * emb_block_linear_plan, emb_stat_rows, emb_stat_rows_launches, emb_mean_fill
- * (additions only).                                                           */
+ * emb_block_linear_plan, emb_stat_rows, emb_stat_rows_launches, emb_mean_fill,
+ * emb_optim_grad_norms, emb_optim_adam_update
+ * (additions only).                                                          */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -832,8 +833,38 @@ int32_t emb_optim_update(const void* table, const void* chunks, int64_t n_chunks
                          float omb1, float c1, float beta2, float omb2, float c2, float eps, float agc, float pmin,
                          float wd, int32_t nesterov, void* stream);
 int32_t emb_optim_metrics(const void* partials, int64_t n_chunks, int64_t count, void* out, void* stream);
-/* Kernel launches the three entry points above have issued in this process,
- * counted where the kernels are launched.                                      */
+/* The PPO learner's chain, ppo/agent.py:114-124, on the same table, chunk map and
+ * partials (emb_optim_table builds them; emb_optim_metrics serves it unchanged):
+ *   optax.clip_by_global_norm, optax.scale_by_adam (eps_root = 0),
+ *   optax.add_decayed_weights, optax.scale_by_learning_rate, optax.apply_updates.
+ * All float32, t the number of this update counted from 1, omb = 1 - beta and
+ * c = 1 - beta^t formed in double by the caller and rounded once:
+ *   gnorm = sqrt(sum over EVERY tensor of sum g^2)            optax.global_norm
+ *   g1  = g if clip == 0 or gnorm < clip, else (g / gnorm) * clip
+ *   mu  = beta1 * mu + omb1 * g1
+ *   nu  = beta2 * nu + omb2 * (g1 * g1)
+ *   u   = (mu / c1) / (sqrt(nu / c2) + eps)
+ *   upd = (u + wd * p where the tensor decays, else u) * -lr ;  p = p + upd
+ * The select is on gnorm < clip: a NaN in ANY gradient makes p, mu and nu NaN in
+ * EVERY tensor (the reference's behaviour, unlike the per-tensor containment of
+ * the chain above); an infinity and no NaN gives g / inf * clip, 0 for the finite
+ * elements and NaN for the infinite ones.
+ *   emb_optim_grad_norms   launch 1: every chunk's sum g^2 into row 0 of
+ *                          `partials`; the parameters are not read
+ *   emb_optim_adam_update  launch 2: every workgroup sums row 0 over all chunks
+ *                          in one fixed order (the same bits and the same clip
+ *                          decision everywhere), then updates its chunks in
+ *                          place; leaves sum upd^2 and sum p_new^2 per chunk in
+ *                          rows 2 and 3
+ * No atomics.  EMB_ERR_INVALID before any launch: a NULL table, chunk map or
+ * partials, n_chunks outside 1 .. 2^31 - 1, a non-finite lr, a beta outside
+ * [0, 1), omb or c outside (0, 1], a negative or non-finite clip, eps or wd.  */
+int32_t emb_optim_grad_norms(const void* table, const void* chunks, int64_t n_chunks, void* partials, void* stream);
+int32_t emb_optim_adam_update(const void* table, const void* chunks, int64_t n_chunks, void* partials, float lr,
+                              float beta1, float omb1, float c1, float beta2, float omb2, float c2, float eps,
+                              float clip, float wd, void* stream);
+/* Kernel launches the five launching entry points above have issued in this
+ * process, counted where the kernels are launched.                             */
 int32_t emb_optim_launches(int64_t* count);
 
 /* ---- Norm followed by the activation, float32 arithmetic on device
