@@ -52,14 +52,20 @@ def _clip_coefficient(grads, clip):
 def _adamw_run(case):
   """p after every step from `torch.optim.AdamW` in float64 on the CPU."""
   c = cases.CASES[case]
-  h, specs, inp = c.hyper, cases.LISTS[c.list], cases.inputs(case)
+  out = adamw_run_over(cases.inputs(case), cases.LISTS[c.list], c.hyper)
+  assert len(out) == cases.STEPS
+  return out
+
+
+def adamw_run_over(inp, specs, h):
+  """The same over any inputs, tensor list and hyper-parameters (tests/test_adam_sweep_host.py runs its lists through it)."""
   params = [torch.from_numpy(x.copy()).double() for x in inp['p']]
   mask = cases.mask_of(specs)
   groups = [{'params': [p for p, m in zip(params, mask) if m], 'weight_decay': h.wd},
             {'params': [p for p, m in zip(params, mask) if not m], 'weight_decay': 0.0}]
   opt = torch.optim.AdamW([g for g in groups if g['params']], lr=1.0, betas=(cases.BETA1, cases.BETA2), eps=cases.EPS)
   out = []
-  for step in range(cases.STEPS):
+  for step in range(len(inp['g'])):
     coefficient = _clip_coefficient(inp['g'][step], h.clip)
     for param, g in zip(params, inp['g'][step]):
       param.grad = torch.from_numpy(g.astype(np.float64) * coefficient)

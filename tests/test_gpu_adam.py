@@ -8,13 +8,19 @@ metrics within 1e-5 + 1e-5 |want|, nu within 1e-5 |want| (floor: the smallest
 normal float32), mu within 1e-5 (|want| + A) with A the same moving average over
 |g1|.  The float32 definition sits inside all of them on every list
 (tests/test_adam_host.py prints its ratios), so no case is exempt.
-tools/adam_accuracy.py records the worst ratios in profiles/adam_accuracy.txt."""
+tools/adam_accuracy.py records the worst ratios in profiles/adam_accuracy.txt.
+
+The last tests run the lists of tests/adam_sweep_cases.py, which take the global-
+norm sum, the grid stride of both kernels and the metrics sum past their first
+iteration, with the clip regime placed on the chunks only a later iteration
+reads and, in the bfloat16 cases of `many`, both gradient dtypes in one list."""
 import numpy as np
 import pytest
 import torch
 
 from embodied_amd.optim import Adam, optimizer_launches        # every test here fails without the feature
 from tests import adam_cases as cases
+from tests import adam_sweep_cases as sweep
 
 pytestmark = pytest.mark.gpu
 PATHS = pytest.mark.parametrize('fused', [True, False], ids=['fused', 'composed'])
@@ -45,9 +51,12 @@ def _params(inp, specs):
 
 
 def _set_grads(params, grads, specs, bf16):
-  for param, g, s in zip(params, grads, specs):
+  """`bf16`: one flag for every gradient, or a sequence of one per tensor."""
+  flags = [bool(bf16)] * len(params) if isinstance(bf16, (bool, np.bool_)) else [bool(flag) for flag in bf16]
+  assert len(flags) == len(params) == len(grads) == len(specs)
+  for param, g, s, flag in zip(params, grads, specs, flags):
     param.grad_dtype = None                        # a float32 parameter may carry a bfloat16 gradient
-    param.grad = _place(g, s.goff, torch.bfloat16 if bf16 else torch.float32)
+    param.grad = _place(g, s.goff, torch.bfloat16 if flag else torch.float32)
 
 
 def _make_from(specs, inp, h, fused, **kw):
@@ -87,7 +96,7 @@ def _run_from(made, steps, grads_of=None):
   opt, params, inp, specs, h = made
   out = []
   for step in range(steps):
-    _set_grads(params, inp['g'][step] if grads_of is None else grads_of(step), specs, h.bf16)
+    _set_grads(params, inp['g'][step] if grads_of is None else grads_of(step), specs, inp.get('bf16', h.bf16))
     opt.step()
     state = _state(opt, params)
     m = opt.metrics()
@@ -310,3 +319,179 @@ def test_a_non_contiguous_parameter_takes_the_composed_path():
   assert torch.allclose(params[1], torch.full((2, 3), -1e-2, device='cuda'), rtol=1e-5)
   contiguous = Adam(_params(inp, specs), fused=None)
   assert contiguous.fused is True
+
+
+# ---- past the first iteration of the kernels' loops: the lists of tests/adam_sweep_cases.py.  `many` has more
+# chunks than kMaxBlocks workgroups, than the metrics kernel has threads and than a workgroup has threads to sum the
+# global norm with; `deep` has more than the last.  The clip regime sits on the chunks only a later iteration reads,
+# and the bfloat16 cases of `many` mix both gradient dtypes within a workgroup.
+
+SWEEP_PATHS = [pytest.param(case, fused, id=f'{sweep.tag(case)}-{"fused" if fused else "composed"}')
+               for case in sweep.CASES for fused in (True, False)]
+SWEEP_LISTS = pytest.mark.parametrize('name', ['many', 'deep'])
+
+
+def _make_sweep(case, fused):
+  name, i = case
+  h = sweep.HYPERS[name][i]
+  return _make_from(sweep.LISTS[name], sweep.inputs(name, h.bf16), h, fused)
+
+
+def _sweep_first(name, **want):
+  """The first sweep case of the list `name` whose hyper-parameters satisfy `want` (truthiness)."""
+  return next(case for case in sweep.CASES
+              if case[0] == name and all(bool(getattr(sweep.HYPERS[name][case[1]], k)) == v for k, v in want.items()))
+
+
+@pytest.mark.parametrize('case,fused', SWEEP_PATHS)
+def test_sweep_lists_against_float64(case, fused):
+  """Every element of p, mu and nu and the four metrics after every step."""
+  name = case[0]
+  specs = sweep.LISTS[name]
+  assert sweep.chunks(sweep.LISTS['many']) > max(sweep.K.values())
+  assert sweep.chunks(sweep.LISTS['deep']) > sweep.K['kThreads']
+  got_all = _run_from(_make_sweep(case, fused), sweep.STEPS[name])
+  want_all = sweep.reference(case)
+  assert len(got_all) == len(want_all) == sweep.STEPS[name] and len(got_all[0]['p']) == len(specs)
+  for step, (got, want) in enumerate(zip(got_all, want_all)):
+    worst = sweep.worst_ratios([got], [want])
+    print(f'{sweep.tag(case)} {"fused" if fused else "composed"}, {sweep.chunks(specs)} chunks, step {step}: ' +
+          ', '.join(f'{k} {v:.3g}' for k, v in worst.items()) + ' of its bar')
+    assert max(worst.values()) <= 1.0, (step, worst)
+
+
+@SWEEP_LISTS
+def test_sweep_lists_take_two_launches_per_step_and_one_for_the_metrics(name):
+  case = _sweep_first(name, clip=True)
+  opt, params, inp, specs, h = _make_sweep(case, True)
+  for step in range(2):
+    _set_grads(params, inp['g'][step], specs, inp['bf16'])
+    before = optimizer_launches()
+    opt.step()
+    assert optimizer_launches() == before + 2, len(params)
+  opt.metrics()
+  assert optimizer_launches() == before + 3
+  composed, cparams, _, _, _ = _make_sweep(case, False)
+  _set_grads(cparams, inp['g'][0], specs, inp['bf16'])
+  before = optimizer_launches()
+  composed.step()
+  composed.metrics()
+  assert optimizer_launches() == before
+
+
+@SWEEP_LISTS
+def test_sweep_lists_identical_state_gives_identical_bits(name):
+  """Every workgroup sums all partials in the same order over more than one round
+  of its threads, and its own chunks over more than one grid pass: the same bits
+  twice, metrics included, with the clip on."""
+  case = _sweep_first(name, clip=True)
+  a, b = (_run_from(_make_sweep(case, True), sweep.STEPS[name]) for _ in range(2))
+  assert len(a) == len(b) == sweep.STEPS[name]
+  for x, y in zip(a, b):
+    assert _same_bits(x, y) and np.array_equal(x['metrics'], y['metrics'])
+
+
+def _poisoned_sweep(case, fused, value, tensor, element, at):
+  """The optimizer and its state after `at + 1` steps, the last one with `value` at one element of one gradient."""
+  opt, params, inp, specs, h = _make_sweep(case, fused)
+  assert h.clip and not h.bf16
+  for step in range(at + 1):
+    grads = [g.copy() for g in inp['g'][step]]
+    if step == at:
+      grads[tensor].reshape(-1)[element] = value
+    _set_grads(params, grads, specs, inp['bf16'])
+    opt.step()
+  return opt, _state(opt, params)
+
+
+@PATHS
+@pytest.mark.parametrize('name', ['many', 'deep'])
+def test_a_nan_only_a_later_loop_iteration_reads_reaches_every_tensor(name, fused):
+  """`many`: the NaN is in the gradient of the last tensor, chunk 2 kMaxBlocks + 2:
+  its workgroup's third, behind kThreads and kMetricThreads in either sum of the
+  partials.  `deep`: in the last element of tensor 0, chunk kThreads + 1, the
+  first one the second round of the global-norm sum reads, in the ragged scalar
+  tail.  One step with the clip on: p, mu and nu are NaN in every element of
+  every tensor and `grad_norm` is NaN."""
+  case = _sweep_first(name, clip=True, bf16=False)
+  specs = sweep.LISTS[name]
+  if name == 'many':
+    tensor, element = len(specs) - 1, 0
+    assert sweep.chunks(specs[:tensor]) == 2 * sweep.BLOCKS + 2 > max(sweep.K.values())
+  else:
+    tensor, element = 0, sweep.DEEP - 1
+    assert element // cases.C == sweep.K['kThreads'] + 1 and sweep.DEEP % 4 == 3      # past the last whole vector
+  opt, got = _poisoned_sweep(case, fused, np.nan, tensor, element, at=0)
+  for key in ('p', 'nu', 'mu'):
+    assert len(got[key]) == len(specs)
+    for i, x in enumerate(got[key]):
+      assert np.isnan(x).all(), (key, i)
+  assert np.isnan(float(opt.metrics()['grad_norm']))
+
+
+@PATHS
+def test_an_infinity_in_a_second_pass_chunk_zeroes_the_finite_elements(fused):
+  """`many`, second step, +inf in tensor kMaxBlocks + 5 (a workgroup's second
+  chunk) and no NaN: gnorm = inf, g / inf * clip is 0 at every finite element of
+  every tensor and NaN at the infinite one, so mu = beta1 mu and nu = beta2 nu of
+  the step before everywhere else, bit for bit."""
+  case = _sweep_first('many', clip=True, bf16=False)
+  tensor, element = sweep.BLOCKS + 5, 0
+  before = _run_from(_make_sweep(case, fused), 1)[0]
+  _, got = _poisoned_sweep(case, fused, np.inf, tensor, element, at=1)
+  for key, beta in (('mu', cases.BETA1), ('nu', cases.BETA2)):
+    for i, (x, old) in enumerate(zip(got[key], before[key])):
+      mask = np.isnan(x).reshape(-1)
+      assert mask.sum() == (1 if i == tensor else 0) and (i != tensor or mask[element]), (key, i, int(mask.sum()))
+      want = (np.float32(beta) * old).reshape(-1)[~mask]          # + (1 - beta) * 0
+      assert np.array_equal(x.reshape(-1)[~mask], want), (key, i)
+  for i, x in enumerate(got['p']):
+    mask = np.isnan(x).reshape(-1)
+    assert mask.sum() == (1 if i == tensor else 0) and (i != tensor or mask[element]), ('p', i)
+
+
+@PATHS
+def test_a_gradient_dtype_that_changes_between_steps(fused):
+  """`sizes`, clip on: float32 gradients on steps 0 and 2, bfloat16 ones (bf16
+  values) on steps 1 and 3, against `restate` in float64 over exactly those
+  values.  Each tensor's gradient lives in one buffer read as either dtype, so no
+  address changes between the steps: the table is uploaded again, four times in
+  all, because a dtype flag differs and for no other reason."""
+  plain_case, rounded_case = _first('sizes', clip=True, bf16=False), _first('sizes', clip=True, bf16=True)
+  h = cases.CASES[rounded_case].hyper
+  specs = cases.LISTS['sizes']
+  plain, rounded = cases.inputs(plain_case), cases.inputs(rounded_case)
+  assert all(np.array_equal(a, b) for a, b in zip(plain['p'], rounded['p']))
+  as_bf16 = (False, True, False, True)
+  inp = {'p': plain['p'], 'g': [(rounded if flag else plain)['g'][step] for step, flag in enumerate(as_bf16)]}
+  for step, flag in enumerate(as_bf16):
+    assert cases.regime(inp['g'][step], h.clip)[1] >= cases.MARGIN
+    assert all(np.array_equal(g, cases.bf16_round(g).reshape(g.shape)) for g in inp['g'][step]) == flag
+  want_all = cases.restate(inp, h, specs, torch.float64)
+  opt, params, _, _, _ = _make_from(specs, inp, h, fused)
+  buffers = [torch.zeros(max(x.size, 1), dtype=torch.float32, device='cuda') for x in inp['p']]
+  before = optimizer_launches()
+  got_all, addresses = [], []
+  for step, flag in enumerate(as_bf16):
+    for param, buffer, g in zip(params, buffers, inp['g'][step]):
+      view = (buffer.view(torch.bfloat16) if flag else buffer)[:g.size].view(g.shape)
+      view.copy_(torch.from_numpy(g.copy()).cuda())          # bfloat16 values: the narrowing is exact
+      param.grad_dtype = None
+      param.grad = view
+    addresses.append([param.grad.data_ptr() for param in params])
+    assert {param.grad.dtype for param in params} == {torch.bfloat16 if flag else torch.float32}
+    opt.step()
+    state = _state(opt, params)
+    m = opt.metrics()
+    state['metrics'] = np.array([float(m[key]) for key in cases.METRICS])
+    got_all.append(state)
+  assert all(a == addresses[0] for a in addresses)
+  for step, (got, want) in enumerate(zip(got_all, want_all)):
+    worst = cases.worst_ratios([got], [want])
+    print(f'sizes, dtype per step {as_bf16}, {"fused" if fused else "composed"} step {step}: ' +
+          ', '.join(f'{k} {v:.3g}' for k, v in worst.items()))
+    assert max(worst.values()) <= 1.0, (step, worst)
+  if fused:
+    assert opt.table_uploads == 4 and optimizer_launches() == before + 3 * 4
+  else:
+    assert opt.table_uploads == 0 and optimizer_launches() == before

@@ -6,8 +6,11 @@ and quantity, as a share of the bars of tests/adam_cases.py.
 Rows: the float32 restatement on the CPU and, on the GPU, the composed path and
 the kernels of csrc/optim.hip, over every case of `cases.CASES` and each of its
 4 steps; every element of p, nu and mu and the four metrics against
-`cases.reference64`, the float64 run that is the definition.  Needs a GPU: there
-is no CPU fallback and no figure without one.
+`cases.reference64`, the float64 run that is the definition.  Below them the same
+three rows for the lists of tests/adam_sweep_cases.py, which take the kernels
+past the first iteration of their loops, over each of their cases and steps
+against `sweep.reference`.  Needs a GPU: there is no CPU fallback and no figure
+without one.
 """
 import argparse
 import pathlib
@@ -19,6 +22,7 @@ sys.path.insert(0, str(ROOT))
 import torch  # noqa: E402
 
 from tests import adam_cases as cases  # noqa: E402
+from tests import adam_sweep_cases as sweep  # noqa: E402
 
 KEYS = ('p', 'nu', 'mu', 'metrics')
 PATHS = ('float32 restated (CPU)', 'composed (GPU)', 'fused (GPU)')
@@ -39,6 +43,18 @@ def main():
       for key, value in cases.worst_ratios(got, want).items():
         slot = (c.list, who, key)
         worst[slot] = max(worst.get(slot, 0.0), value)
+  deeper = {}
+  for case in sweep.CASES:
+    name, i = case
+    h = sweep.HYPERS[name][i]
+    want = sweep.reference(case)
+    runs = {'float32 restated (CPU)': cases.restate(sweep.inputs(name, h.bf16), h, sweep.LISTS[name], torch.float32),
+            'composed (GPU)': gpu._run_from(gpu._make_sweep(case, False), sweep.STEPS[name]),
+            'fused (GPU)': gpu._run_from(gpu._make_sweep(case, True), sweep.STEPS[name])}
+    for who, got in runs.items():
+      for key, value in sweep.worst_ratios(got, want).items():
+        slot = (name, who, key)
+        deeper[slot] = max(deeper.get(slot, 0.0), value)
   lines = ['# tools/adam_accuracy.py',
            f'# {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), torch {torch.__version__}',
            f'# {len(cases.CASES)} cases x {cases.STEPS} steps; worst |got - float64| as a share of the bar, every element:',
@@ -51,7 +67,17 @@ def main():
   for who in PATHS:
     lines.append(f'  {"all":<10}{who:<26}' +
                  ''.join(f'{max(worst[(name, who, key)] for name in cases.LISTS):<12.3g}' for key in KEYS))
-  over = sorted(slot for slot, value in worst.items() if value > 1.0)
+  k = sweep.K
+  lines += ["# ---- past the first iteration of the kernels' loops (lists of tests/adam_sweep_cases.py; the same bars):",
+            f'#   many: {len(sweep.LISTS["many"])} tensors of 1 .. 5 elements, {sweep.chunks(sweep.LISTS["many"])} chunks (kMaxBlocks = '
+            f'{k["kMaxBlocks"]}, kMetricThreads = {k["kMetricThreads"]}, kThreads = {k["kThreads"]}),',
+            f'#     {len(sweep.HYPERS["many"])} cases x {sweep.STEPS["many"]} steps, the bfloat16 cases with bfloat16 gradients in every third tensor only;',
+            f'#   deep: two tensors of {k["kThreads"] + 2} chunks and one of 3 elements, {sweep.chunks(sweep.LISTS["deep"])} chunks, '
+            f'{len(sweep.HYPERS["deep"])} cases x {sweep.STEPS["deep"]} steps']
+  for name in sweep.LISTS:
+    for who in PATHS:
+      lines.append(f'  {name:<10}{who:<26}' + ''.join(f'{deeper[(name, who, key)]:<12.3g}' for key in KEYS))
+  over = sorted(slot for slot, value in list(worst.items()) + list(deeper.items()) if value > 1.0)
   lines.append('# over a bar: ' + (', '.join(' / '.join(slot) for slot in over) or 'nothing'))
   print('\n'.join(lines), flush=True)
   out = pathlib.Path(args.out)
