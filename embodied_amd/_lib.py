@@ -72,6 +72,15 @@ class ObsSpec(C.Structure):
       ('out_dtype', C.c_int32), ('scale', C.c_float), ('offset', C.c_float)]
 
 
+class SynthStep(C.Structure):
+  """emb_synth_step_t: the masked env step's arguments (emb_synth_env_step_fused)."""
+  _fields_ = [
+      ('image', C.c_void_p), ('reward', C.c_void_p), ('is_first', C.c_void_p), ('is_last', C.c_void_p),
+      ('is_terminal', C.c_void_p), ('n', C.c_int64), ('frame_bytes', C.c_int64), ('env0', C.c_int64),
+      ('episode_len', C.c_int64), ('reset', C.c_void_p), ('counters', C.c_void_p), ('act', C.c_void_p),
+      ('masked_out', C.c_void_p), ('row_bytes', C.c_int64), ('turn', C.c_int32), ('dtype', C.c_int32)]
+
+
 class NormalizeConfig(C.Structure):
   """emb_normalize_config_t: the hyper-parameters of emb_normalize."""
   _fields_ = [
@@ -272,6 +281,7 @@ SIGNATURES = {
     'emb_synth_env_step': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p],
     'emb_synth_env_step_masked': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p, p, i64, i32, p],
     'emb_env_mask_supported': [i64, i32],
+    'emb_synth_env_step_fused': [p, i64, p, i32, p, p, p, p, p, p],
     'emb_comm_unique_id': [p],
     'emb_comm_init': [p, i32, i32, pp],
     'emb_comm_allgather_traj': [p, p, p, i64, p],
@@ -396,6 +406,7 @@ class _FastApi:
 
   SHAPES = {
       'emb_synth_env_step': 'ints', 'emb_mask_actions': 'ints', 'emb_synth_env_step_masked': 'ints',
+      'emb_synth_env_step_fused': 'ints',
       'emb_replay_add': 'ints', 'emb_replay_add_masked': 'ints',
       'emb_replay_obs_stack_insert': 'ints', 'emb_replay_publish': 'ints',
       'emb_replay_sample': 'ints', 'emb_replay_sample_grouped': 'ints', 'emb_replay_update': 'ints',

@@ -200,6 +200,7 @@ class Driver:
     self._acts = None         # what `acts` returns; the stepping loop uses this name
     self._pending = None      # raw actions the env's next step launch has yet to mask into _acts
     self._env_masks = False
+    self._stacks_in_step = False     # ... and its launch may make the obs stack + early insert too
     self.carry = None
     self._slab = {}
     self._obs_names, self._obs_has_logs = None, False
@@ -588,7 +589,21 @@ class Driver:
     the mask runs unconditionally (a no-op where nothing ended) and episodes
     are counted only when the caller stops on them."""
     pending = self._pending
-    if pending is None:
+    fused = False
+    if (pending is not None and self._stacks_in_step and len(self._sinks) == 1
+        and not self._obs_has_logs):        # (what makes `sink` below the step's only consumer)
+      # An env whose step launch can also build the policy batch and make the
+      # early insert (`stacks_obs_in_step`): the Replay is asked first -- it knows
+      # the rows and how the agent stacked this ring slot's frames the last time
+      # (ops.obs_stack's memo).  One launch; refused: the two launches below.
+      peek = self.batch_env.peek_fused(self._acts, pending)
+      if peek is not None and self._sinks[0].step_fused(peek[0], self._workers, peek[1], peek[2]):
+        self.batch_env.commit_fused()
+        self._pending = None
+        obs, fused = peek[0], True
+    if fused:
+      pass
+    elif pending is None:
       obs = self.batch_env.step(self._acts)
     else:
       # (env-masked form: this launch stores pending * ~reset into _acts' tensors)
@@ -609,7 +624,7 @@ class Driver:
     # the next step's actions both receive value * ~is_last) instead of taking a
     # launch of its own.
     sink = self._sinks[0] if len(self._sinks) == 1 and not logs else None
-    if sink is not None and _EARLY_INSERT:
+    if sink is not None and _EARLY_INSERT and not fused:
       sink.offer(obs, self._workers)
     if self.kwargs:
       self.carry, acts, outs = policy(self.carry, obs, **self.kwargs)
@@ -649,6 +664,9 @@ class Driver:
             and hasattr(sink, 'carry_publish') and hasattr(sink, 'add_step'))
         if self._env_masks:
           sink.carry_publish(True)
+        self._stacks_in_step = bool(
+            self._env_masks and _EARLY_INSERT and getattr(self.batch_env, 'stacks_obs_in_step', False)
+            and hasattr(sink, 'step_fused'))
       if self._env_masks and not self._unmasked:
         dst = self._mask_dst(acts)
         if dst is not None:

@@ -66,7 +66,7 @@ class _StepRecord:
   stacks it the same way into the same staging tensor, all the per-key checks
   and pointer look-ups of the general path have been done before."""
   __slots__ = ('owner', 'values', 'workers', 'workers_ptr', 'n', 'frame_key', 'frames_ptr',
-               'early_ptrs', 'memo', 'spec', 'out_ptr', 'publishes')
+               'early_ptrs', 'memo', 'spec', 'out_ptr', 'publishes', 'no_fuse')
 
 
 def _itemsize(dtype):
@@ -198,6 +198,8 @@ class Replay:
     self._carrying, self._carry_keep, self._carry_tmp = False, None, None
     self._token = C.c_uint64()
     self.early_inserts = 0          # steps whose observation keys went in with the obs stack
+    self.fused_steps = 0            # ... of which the env's own step launch wrote them (step_fused)
+    self._fused_memo = None         # the obs_stack memo the standing fused step was launched with
     self._savers = concurrent.futures.ThreadPoolExecutor(16, 'replay_saver')
     if directory and self._owners == 1 and pathlib.Path(directory).is_dir():
       self._reserve_directory_uids(directory)
@@ -648,6 +650,7 @@ class Replay:
     self._offer_workers = workers
     self._pre_token = 0
     self._cur_rec = None
+    self._fused_memo = None
     order = tuple(obs)
     names = self._offer_names.get(order)
     if names is None:
@@ -660,12 +663,60 @@ class Replay:
       if getattr(frames, '_emb_offer', None) is not tag:
         frames._emb_offer = tag
 
+  def step_fused(self, obs, workers, env_step, arm=None):
+    """Driver -> Replay BEFORE a device env's step (`stacks_obs_in_step`): `obs`
+    are the tensors the step is about to write, `env_step` the address of its
+    emb_synth_step_t.  True: ONE launch has made the env's step, the policy batch
+    and the early insert of the step (emb_synth_env_step_fused) -- this call then
+    stands for the env's step and for `offer` + the agent's `ops.obs_stack`, which
+    returns its `out` without a launch (only a staging tensor the agent handed in
+    as `out=` is written ahead like this, never a batch obs_stack allocated).  That takes a step record on the frame
+    tensor (this ring slot went through `_early_insert` before, stacked the way
+    its `_emb_stack` memo says) and rows the library has predicted; otherwise
+    False, nothing has happened, and the step is the two launches.  `arm`: called
+    right before the launch is asked for (the env's last-moment preparations)."""
+    if self._keys is None or self._staged or not self._carrying:
+      return False
+    rec = memo = None
+    for name in self._offer_names.get(tuple(obs), ()):
+      attrs = obs[name].__dict__
+      rec, memo = attrs.get('_emb_rec'), attrs.get('_emb_stack')
+      if rec is not None:
+        break
+    if (rec is None or memo is None or rec.memo is not memo or not memo[9] or rec.no_fuse
+        or rec.owner is not self._offer_tag
+        or workers is not rec.workers or not fast.same_values(obs, rec.values)):
+      return False
+    with self._lock:
+      if self._staged:
+        return False
+      if arm is not None:
+        arm()
+      try:
+        fast.emb_synth_env_step_fused(
+            self._h, rec.n, rec.workers_ptr, rec.frame_key, env_step, rec.spec, rec.out_ptr,
+            rec.early_ptrs, self._stream(), self._token)
+      except ValueError:
+        rec.no_fuse = True               # the launch does not take this step at all: not asked again
+        return False
+      token = self._token.value
+      if not token:
+        return False
+      self._offer_obs, self._offer_workers = obs, workers
+      self._pre_token, self._cur_rec, self._fused_memo = token, rec, memo
+      self.early_inserts += 1
+      self.fused_steps += 1
+    return True
+
   def _early_insert(self, frames, pixels, channels, first, dtype, scale, offset, out, memo=None):
     """ops.obs_stack on an offered frame tensor.  True: the policy batch has
     been written (with or without the early insert); False: not handled.
     `memo`: ops.obs_stack's note on the frame tensor (same object = same options
     and staging tensor as when it was made)."""
     obs = self._offer_obs
+    if (self._pre_token and memo is not None and memo is self._fused_memo
+        and frames.__dict__.get('_emb_rec') is self._cur_rec):
+      return True          # the env's step launch wrote this very batch into `out` (step_fused)
     if obs is None or self._pre_token or self._keys is None:
       return False
     rec = frames.__dict__.get('_emb_rec')
@@ -742,6 +793,7 @@ class Replay:
           rec.early_ptrs = (C.c_void_p * len(self._keys))(*self._early_ptrs)
           rec.memo, rec.spec, rec.out_ptr = memo, spec[1], out.data_ptr()
           rec.publishes = {}
+          rec.no_fuse = False
           frames._emb_rec = rec
           self._cur_rec = rec
     return True
@@ -1374,7 +1426,7 @@ class Replay:
     carried publishes -- in the `ms` position)."""
     launches, ms, name = C.c_int64(), C.c_double(), C.create_string_buffer(128)
     api.emb_replay_profile_report(
-        self._handle, {'sample': 0, 'update': 1, 'deferred': 2, 'carried': 3}[which], C.byref(launches), C.byref(ms),
+        self._handle, {'sample': 0, 'update': 1, 'deferred': 2, 'carried': 3, 'fused': 4}[which], C.byref(launches), C.byref(ms),
         int(reset), name, len(name))
     return launches.value, ms.value, name.value.decode()
 

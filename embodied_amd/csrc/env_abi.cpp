@@ -73,4 +73,58 @@ int32_t emb_synth_env_step_masked(void* image, void* reward, void* is_first, voi
   });
 }
 
+// EMB_STEP_FUSED=0: the env step and the early insert stay two launches.
+static bool step_fused() {
+  static const bool on = [] {
+    const char* v = emb::knob("EMB_STEP_FUSED");
+    return !(v && v[0] == '0');
+  }();
+  return on;
+}
+
+int32_t emb_synth_env_step_fused(emb_replay_t* rep, int64_t n, const int64_t* workers, int32_t frame_key,
+                                 const emb_synth_step_t* env, const emb_obs_spec_t* spec, void* dst,
+                                 const void* const* src, void* stream, uint64_t* token_out) {
+  return guarded([&] {
+    need(rep && env && token_out, "synth_env_step_fused: bad arguments");
+    *token_out = 0;
+    if (!step_fused()) return;
+    emb::SynthStepArgs a;
+    a.image = static_cast<uint8_t*>(env->image);
+    a.reward = static_cast<float*>(env->reward);
+    a.is_first = static_cast<uint8_t*>(env->is_first);
+    a.is_last = static_cast<uint8_t*>(env->is_last);
+    a.is_terminal = static_cast<uint8_t*>(env->is_terminal);
+    a.n = env->n;
+    a.frame_bytes = env->frame_bytes;
+    a.env0 = env->env0;
+    a.episode_len = env->episode_len;
+    a.reset = static_cast<const uint8_t*>(env->reset);
+    a.counters = static_cast<int32_t*>(env->counters);
+    a.turn = env->turn;
+    a.act = env->act;
+    a.masked_out = env->masked_out;
+    a.row_bytes = env->row_bytes;
+    a.dtype = env->dtype;
+    need(n == env->n && n > 0, "synth_env_step_fused: the replay's workers are not the env's n envs");
+    need(a.dtype >= 0 && a.dtype <= emb::kBool, "synth_env_step_fused: bad action dtype");
+    StepLaunch step;
+    step.ctx = &a;
+    step.refusal = [](void* ctx, const emb::PrewritePlan& plan) {
+      return emb::synth_fused_refusal(*static_cast<emb::SynthStepArgs*>(ctx), plan);
+    };
+    step.bytes = [](void*, int64_t n_envs) { return emb::synth_fused_block_bytes(n_envs); };
+    step.fill = [](void* ctx, void* block, const emb::PrewritePlan& plan, const int32_t* rows,
+                   const uint8_t* stepids) {
+      emb::synth_fused_fill(block, *static_cast<emb::SynthStepArgs*>(ctx), plan, rows, stepids);
+    };
+    step.launch = [](void* ctx, const emb::PrewritePlan& plan, hipStream_t s, hipEvent_t stop) {
+      return emb::launch_synth_env_fused(*static_cast<emb::SynthStepArgs*>(ctx), plan, plan.table_dev, s, stop);
+    };
+    HostLap hp;
+    replay_early_insert(rep, n, workers, frame_key, env->image, spec, dst, src, stream, token_out, &step);
+    hp.lap(21, "synthetic env: launch");
+  });
+}
+
 }  // extern "C"

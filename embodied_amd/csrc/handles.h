@@ -114,6 +114,8 @@ struct emb_replay {
   } predict;
   uint64_t epoch = 0;               // operations on this handle so far (REP_OP)
   int64_t predicted_inserts = 0;
+  int64_t insert_launches = 0;       // obs_stack_insert_kernel launches (early inserts with a launch of their own)
+  int64_t fused_steps = 0;           // early inserts made by the device env's own step launch (StepLaunch)
   int32_t* dev_rows = nullptr;       // the prewrite launch's rows, for the publish launch
   size_t dev_rows_cap = 0;
 
@@ -153,3 +155,20 @@ struct emb_replay {
   }
   std::vector<std::pair<hipStream_t, std::unique_ptr<ArgRing>>> arg_rings;
 };
+
+// An early insert whose launch belongs to someone else: the device env's fused
+// step (env_abi.cpp) hands these to replay_early_insert, which keeps everything
+// the following publish or carry needs -- rows, token, carried state, stream
+// order -- exactly as for its own launch.  `refusal`: why this plan cannot be
+// launched (null = it can); bytes / fill: the device block (the plan's table
+// inside it); launch: the kernel, with plan.table_dev = the block.
+struct StepLaunch {
+  void* ctx;
+  const char* (*refusal)(void* ctx, const emb::PrewritePlan& plan);
+  size_t (*bytes)(void* ctx, int64_t n);
+  void (*fill)(void* ctx, void* block, const emb::PrewritePlan& plan, const int32_t* rows, const uint8_t* stepids);
+  hipError_t (*launch)(void* ctx, const emb::PrewritePlan& plan, hipStream_t stream, hipEvent_t stop);
+};
+void replay_early_insert(emb_replay* rep, int64_t n, const int64_t* workers, int32_t frame_key,
+                         const void* frames, const emb_obs_spec_t* spec, void* dst, const void* const* src,
+                         void* stream, uint64_t* token_out, const StepLaunch* step);

@@ -242,6 +242,38 @@ bool prewrite_supported(const PrewritePlan& plan);
 size_t prewrite_table_bytes(int64_t n);
 void prewrite_fill_table(void* dst, const PrewritePlan& plan, const int32_t* rows, const uint8_t* stepids);
 hipError_t launch_obs_stack_insert(const PrewritePlan& plan, hipStream_t stream, hipEvent_t stop = nullptr);
+
+// The device env's step, the obs stack and the early insert in ONE launch: the
+// workgroup that generates 16 bytes of a frame stores them to the env's image
+// buffer, to the frame's pool row and, cast per channel, to the policy batch;
+// the env's narrow workgroup does the episode logic, the action mask, and writes
+// reward and flags to the env's buffers AND to their pool rows from registers.
+// `plan` is the early insert's (frames = the env's image buffer, 4 channels;
+// every narrow key's source one of the env's reward / flag buffers).  The device
+// block -- synth_fused_block_bytes(n) bytes, filled by synth_fused_fill -- is a
+// head (mask job, the scalars that do not fit the 14 preloaded dwords) followed
+// by the early insert's table exactly as prewrite_fill_table lays it out.
+struct SynthStepArgs {
+  uint8_t* image = nullptr;
+  float* reward = nullptr;
+  uint8_t *is_first = nullptr, *is_last = nullptr, *is_terminal = nullptr;
+  int64_t n = 0, frame_bytes = 0, env0 = 0, episode_len = 0;
+  const uint8_t* reset = nullptr;
+  int32_t* counters = nullptr;
+  int turn = 0;
+  const void* act = nullptr;         // the mask job: raw actions -> masked_out
+  void* masked_out = nullptr;
+  int64_t row_bytes = 0;
+  int dtype = kU8;
+};
+constexpr size_t kSynthFusedHeadBytes = 96;
+// Why a fused launch cannot be made (null = it can): nothing is launched then.
+const char* synth_fused_refusal(const SynthStepArgs& env, const PrewritePlan& plan);
+size_t synth_fused_block_bytes(int64_t n);
+void synth_fused_fill(void* dst, const SynthStepArgs& env, const PrewritePlan& plan, const int32_t* rows,
+                      const uint8_t* stepids);
+hipError_t launch_synth_env_fused(const SynthStepArgs& env, const PrewritePlan& plan, const void* block_dev,
+                                  hipStream_t stream, hipEvent_t stop = nullptr);
 // One key of n rows to the pool rows `rows_dev` (device int32[n], -1 = skip):
 // value * !flags[r] in `dtype` when flags is set (and to `out` as well), a plain
 // copy otherwise.  flags_by_row: `flags` is a pool of 1-byte rows and row r's

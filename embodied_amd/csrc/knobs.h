@@ -21,7 +21,7 @@ namespace emb {
 // name, so a misspelt or retired knob is an error instead of a silent no-op.
 constexpr const char* kKnobNames[] = {
     "EMB_ARGS_BAR",     "EMB_DEFER_INDEX", "EMB_DEFER_MAX_GAP_US", "EMB_GATHER_STORES", "EMB_HOST_PROFILE",
-    "EMB_PREDICT_ROWS", "EMB_RCCL_LIB",    "EMB_SPAN_MOVER",       "EMB_WHERE_BACKLOG",
+    "EMB_PREDICT_ROWS", "EMB_RCCL_LIB",    "EMB_SPAN_MOVER",       "EMB_STEP_FUSED",       "EMB_WHERE_BACKLOG",
 };
 inline bool knob_known(const char* name) {
   for (const char* known : kKnobNames)

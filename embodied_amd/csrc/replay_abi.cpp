@@ -598,11 +598,16 @@ int32_t emb_replay_publish(emb_replay_t* rep, int64_t n, const int64_t* workers,
                     static_cast<hipStream_t>(stream), token));
 }
 
-int32_t emb_replay_obs_stack_insert(emb_replay_t* rep, int64_t n, const int64_t* workers,
-                                    int32_t frame_key, const void* frames, const emb_obs_spec_t* spec,
-                                    void* dst, const void* const* src, void* stream,
-                                    uint64_t* token_out) {
-  return guarded([&] {
+}  // extern "C"
+
+// The early insert; with `step` (handles.h StepLaunch) the launch, its device
+// block and the last word on whether it can be made are the caller's: the device
+// env's fused step (env_abi.cpp).  Such a call goes ahead only on predicted rows
+// and otherwise returns with *token_out = 0 and this handle untouched.
+void replay_early_insert(emb_replay* rep, int64_t n, const int64_t* workers, int32_t frame_key,
+                         const void* frames, const emb_obs_spec_t* spec, void* dst, const void* const* src,
+                         void* stream, uint64_t* token_out, const StepLaunch* step) {
+  {
     need(rep, "replay handle is null");
     std::lock_guard<std::mutex> lock(rep->mu);
     std::lock_guard<std::mutex> sel_lock(*rep->selector_mu);
@@ -613,6 +618,63 @@ int32_t emb_replay_obs_stack_insert(emb_replay_t* rep, int64_t n, const int64_t*
     const bool predicted = known.valid && known.epoch == rep->epoch && workers && n > 0 &&
                            static_cast<int64_t>(known.workers.size()) == n &&
                            std::equal(workers, workers + n, known.workers.begin());
+    const int n_keys = static_cast<int>(rep->keys.size());
+    // The plan as far as the arguments alone decide it (no state is read but the
+    // key table): the frame key, the narrow keys that ride along, the step ids.
+    // `marks`: per replay key the buffer it is written from (Prewritten::src).
+    auto plan_keys = [&](emb::PrewritePlan& plan, std::vector<const void*>& marks) {
+      plan.frames = static_cast<const uint8_t*>(frames);
+      plan.dst = dst;
+      plan.pixels = spec->pixels;
+      plan.channels = spec->channels;
+      plan.layout = spec->layout;
+      plan.out_dtype = spec->out_dtype;
+      plan.scale = spec->scale;
+      plan.offset = spec->offset;
+      plan.n = static_cast<int32_t>(n);
+      if (!(frame_key >= 0 && frame_key < n_keys && frame_key != rep->key_stepid &&
+            rep->keys[frame_key].pool && src[frame_key] == frames &&
+            rep->keys[frame_key].rowbytes == spec->pixels * spec->channels && n <= INT32_MAX))
+        return false;
+      plan.frame_pool = rep->keys[frame_key].pool;
+      marks.assign(n_keys, nullptr);
+      marks[frame_key] = frames;
+      for (int k = 0; k < n_keys; ++k) {
+        if (k == frame_key) continue;
+        if (k == rep->key_stepid) {
+          plan.stepid_pool = rep->keys[k].pool;
+          marks[k] = rep->keys[k].pool;       // any non-null mark: step ids have no source buffer
+          continue;
+        }
+        // Narrow observation keys the caller listed ride along; wide ones and
+        // everything not listed (actions, agent outputs) wait for the publish.
+        if (!src[k] || !rep->keys[k].pool || rep->keys[k].rowbytes > 256 ||
+            plan.n_narrow >= emb::kPreNarrow)
+          continue;
+        plan.narrow[plan.n_narrow++] = {static_cast<const uint8_t*>(src[k]), rep->keys[k].pool,
+                                        rep->keys[k].rowbytes};
+        marks[k] = src[k];
+      }
+      return true;
+    };
+    emb::PrewritePlan plan;
+    std::vector<const void*> marks;
+    bool planned = false, early = false;
+    if (step) {
+      // Somebody else's launch: everything that can say no is asked BEFORE this
+      // handle changes -- not predicted: *token_out = 0; a step the launch cannot
+      // take: an error.  Either way the prediction stands for the two launches.
+      need(token_out, "early insert: null token");
+      *token_out = 0;
+      if (!predicted) return;
+      need(frames && spec && dst && src && spec->pixels > 0 && spec->channels > 0 &&
+               (spec->layout == EMB_LAYOUT_SAME || spec->layout == EMB_LAYOUT_CHANNELS_FIRST),
+           "early insert: bad arguments");
+      early = plan_keys(plan, marks) && emb::prewrite_supported(plan);
+      const char* refusal = early ? step->refusal(step->ctx, plan) : "the frame key is not this replay's";
+      need(!refusal, refusal ? refusal : "");
+      planned = true;
+    }
     known.valid = false;
     if (!predicted) {
       rep->gate->drain();
@@ -629,20 +691,7 @@ int32_t emb_replay_obs_stack_insert(emb_replay_t* rep, int64_t n, const int64_t*
     HostLap hp;
     emb_replay::Prewritten& pre = rep->pre;
     pre.token = 0;
-    const int n_keys = static_cast<int>(rep->keys.size());
-    emb::PrewritePlan plan;
-    plan.frames = static_cast<const uint8_t*>(frames);
-    plan.dst = dst;
-    plan.pixels = spec->pixels;
-    plan.channels = spec->channels;
-    plan.layout = spec->layout;
-    plan.out_dtype = spec->out_dtype;
-    plan.scale = spec->scale;
-    plan.offset = spec->offset;
-    plan.n = static_cast<int32_t>(n);
-    bool early = frame_key >= 0 && frame_key < n_keys && frame_key != rep->key_stepid &&
-                 rep->keys[frame_key].pool && src[frame_key] == frames &&
-                 rep->keys[frame_key].rowbytes == spec->pixels * spec->channels && n <= INT32_MAX;
+    if (!planned) early = plan_keys(plan, marks);
     if (early && predicted) {
       rep->rows = known.rows;
       rep->ids = known.ids;
@@ -660,26 +709,8 @@ int32_t emb_replay_obs_stack_insert(emb_replay_t* rep, int64_t n, const int64_t*
     }
     hp.lap(4, "early insert: peek");
     if (early) {
-      plan.frame_pool = rep->keys[frame_key].pool;
-      pre.src.assign(n_keys, nullptr);
-      pre.src[frame_key] = frames;
-      for (int k = 0; k < n_keys; ++k) {
-        if (k == frame_key) continue;
-        if (k == rep->key_stepid) {
-          plan.stepid_pool = rep->keys[k].pool;
-          pre.src[k] = rep->keys[k].pool;       // any non-null mark: step ids have no source buffer
-          continue;
-        }
-        // Narrow observation keys the caller listed ride along; wide ones and
-        // everything not listed (actions, agent outputs) wait for the publish.
-        if (!src[k] || !rep->keys[k].pool || rep->keys[k].rowbytes > 256 ||
-            plan.n_narrow >= emb::kPreNarrow)
-          continue;
-        plan.narrow[plan.n_narrow++] = {static_cast<const uint8_t*>(src[k]), rep->keys[k].pool,
-                                        rep->keys[k].rowbytes};
-        pre.src[k] = src[k];
-      }
-      early = emb::prewrite_supported(plan);
+      pre.src = marks;
+      if (!planned) early = emb::prewrite_supported(plan);
     }
     emb_replay::Carried& carried = rep->carry;
     if (carried.active && !(early && carried.stream == s && carried.n == n)) settle_carry(rep, predicted);
@@ -710,26 +741,36 @@ int32_t emb_replay_obs_stack_insert(emb_replay_t* rep, int64_t n, const int64_t*
     hp.lap(5, "early insert: key plan");
     // The per-env table goes to device memory: written by the CPU through the
     // BAR when it fits a slot of the argument ring, else staged and copied.
-    const size_t bytes = emb::prewrite_table_bytes(n);
+    const size_t bytes = step ? step->bytes(step->ctx, n) : emb::prewrite_table_bytes(n);
     const uint8_t* ids = reinterpret_cast<const uint8_t*>(rep->ids.data());
+    auto fill = [&](void* block) {
+      if (step) step->fill(step->ctx, block, plan, rep->rows.data(), ids);
+      else emb::prewrite_fill_table(block, plan, rep->rows.data(), ids);
+    };
     TableRing::Lease lease{-1, nullptr, nullptr};
     bool in_bar = false;
     ArgRing& arg_ring = rep->args_for(s);
     if (bytes <= ArgRing::kSlotBytes && arg_ring.usable()) {
       uint8_t* slot = arg_ring.take(s);
-      emb::prewrite_fill_table(slot, plan, rep->rows.data(), ids);
+      fill(slot);
       ArgRing::publish();
       plan.table_dev = slot;
       in_bar = true;
     } else {
       lease = rep->ring.acquire(bytes, s);
-      emb::prewrite_fill_table(lease.host, plan, rep->rows.data(), ids);
+      fill(lease.host);
       rep->ring.upload(lease, bytes, s);
       plan.table_dev = lease.device;
     }
     hp.lap(6, "early insert: table -> device");
     rep->order_before(StreamOrder::kWriteFresh, s, predicted);
-    HIP_OK(emb::launch_obs_stack_insert(plan, s, write_stamp(rep)));
+    if (step) {
+      HIP_OK(step->launch(step->ctx, plan, s, write_stamp(rep)));
+      rep->fused_steps += 1;
+    } else {
+      HIP_OK(emb::launch_obs_stack_insert(plan, s, write_stamp(rep)));
+      rep->insert_launches += 1;
+    }
     rep->order_after(StreamOrder::kWriteFresh, s);
     if (carried.active) {
       carried.active = false;
@@ -744,6 +785,17 @@ int32_t emb_replay_obs_stack_insert(emb_replay_t* rep, int64_t n, const int64_t*
     pre.token = ++rep->pre_serial;
     *token_out = pre.token;
     hp.lap(8, "early insert: retire + record");
+  }
+}
+
+extern "C" {
+
+int32_t emb_replay_obs_stack_insert(emb_replay_t* rep, int64_t n, const int64_t* workers,
+                                    int32_t frame_key, const void* frames, const emb_obs_spec_t* spec,
+                                    void* dst, const void* const* src, void* stream,
+                                    uint64_t* token_out) {
+  return guarded([&] {
+    replay_early_insert(rep, n, workers, frame_key, frames, spec, dst, src, stream, token_out, nullptr);
   });
 }
 
@@ -981,7 +1033,7 @@ int32_t emb_replay_profile(emb_replay_t* rep, int32_t enable) {
 int32_t emb_replay_profile_report(emb_replay_t* rep, int32_t which, int64_t* launches, double* total_ms,
                                   int32_t reset, char* kernel_out, int32_t kernel_cap) {
   REP_OP({
-    need(launches && total_ms && which >= 0 && which <= 3, "profile_report: bad arguments");
+    need(launches && total_ms && which >= 0 && which <= 4, "profile_report: bad arguments");
     static const std::string helper_name = "index bookkeeping on the helper thread";
     static const std::string carried_name = "publishes carried into the next early-insert launch (total_ms: of how many carried)";
     if (which == 2) {                    // not a kernel: publishes deferred to the helper thread
@@ -992,11 +1044,17 @@ int32_t emb_replay_profile_report(emb_replay_t* rep, int32_t which, int64_t* lau
       *launches = rep->carried_inline;
       *total_ms = static_cast<double>(rep->carried_total);
       if (reset) rep->carried_inline = rep->carried_total = 0;
+    } else if (which == 4) {             // the device env's fused step launches (each one an early insert too)
+      *launches = rep->fused_steps;
+      *total_ms = static_cast<double>(rep->insert_launches);    // obs_stack_insert launches of its own
+      if (reset) rep->fused_steps = rep->insert_launches = 0;
     } else {
       (which == 0 ? rep->timer : rep->timer_update).read(launches, total_ms, reset != 0);
     }
     if (kernel_out && kernel_cap > 0) {
-      const std::string& name = which == 2 ? helper_name : which == 3 ? carried_name : rep->timed_kernel[which];
+      static const std::string fused_name = "env steps that made the early insert in their own launch (total_ms: obs_stack_insert launches)";
+      const std::string& name = which == 2 ? helper_name : which == 3 ? carried_name
+                                : which == 4 ? fused_name : rep->timed_kernel[which];
       const size_t n = std::min<size_t>(name.size(), static_cast<size_t>(kernel_cap) - 1);
       std::memcpy(kernel_out, name.data(), n);
       kernel_out[n] = 0;

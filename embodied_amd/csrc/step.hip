@@ -1,9 +1,8 @@
 // Driver step: obs stack (+ early insert into the replay), publish of the action,
 // action mask, windowing and the byte copy.
 #include "device_util.h"
+#include "step_device.h"
 
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -14,38 +13,6 @@ namespace emb {
 namespace {
 
 // ---------------------------------------------------------------- obs stack --
-
-template <typename Out>
-__device__ __forceinline__ Out cvt(uint8_t v, float scale, float offset);
-template <> __device__ __forceinline__ uint8_t cvt<uint8_t>(uint8_t v, float, float) { return v; }
-template <> __device__ __forceinline__ float cvt<float>(uint8_t v, float s, float o) { return fmaf(static_cast<float>(v), s, o); }
-template <> __device__ __forceinline__ __half cvt<__half>(uint8_t v, float s, float o) { return __float2half(fmaf(static_cast<float>(v), s, o)); }
-template <> __device__ __forceinline__ __hip_bfloat16 cvt<__hip_bfloat16>(uint8_t v, float s, float o) { return __float2bfloat16(fmaf(static_cast<float>(v), s, o)); }
-
-template <typename Out>
-struct alignas(4 * sizeof(Out)) Quad { Out v[4]; };
-
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-// Streaming store of one Quad (4, 8 or 16 bytes): the policy batch is consumed
-// by another kernel, keeping it dirty in this XCD's L2 only delays the next
-// kernel boundary.
-template <typename Out>
-__device__ __forceinline__ void store_quad(Out* dst, const Quad<Out>& q) {
-  if constexpr (sizeof(Quad<Out>) == 4) {
-    uint32_t w;
-    __builtin_memcpy(&w, &q, 4);
-    __builtin_nontemporal_store(w, reinterpret_cast<uint32_t*>(dst));
-  } else if constexpr (sizeof(Quad<Out>) == 8) {
-    u32x2 w;
-    __builtin_memcpy(&w, &q, 8);
-    __builtin_nontemporal_store(w, reinterpret_cast<u32x2*>(dst));
-  } else {
-    u32x4 w;
-    __builtin_memcpy(&w, &q, 16);
-    __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(dst));
-  }
-}
 
 // Each lane owns 4 consecutive pixels of one frame: it reads their 4*C bytes as
 // C dwords (coalesced across lanes) and writes, per channel, one 4-element
@@ -64,26 +31,7 @@ __global__ __launch_bounds__(kThreads) void obs_stack_kernel(
     uint32_t w[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) w[c] = frame[q * C + c];
-    auto byte_at = [&w](int idx) {
-      return static_cast<uint8_t>((w[idx >> 2] >> ((idx & 3) * 8)) & 0xFFu);
-    };
-    if (kChannelsFirst) {
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        Quad<Out> o;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) o.v[p] = cvt<Out>(byte_at(p * C + c), scale, offset);
-        store_quad(out + c * pixels + q * 4, o);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < C; ++j) {
-        Quad<Out> o;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) o.v[p] = cvt<Out>(byte_at(j * 4 + p), scale, offset);
-        store_quad(out + (q * C + j) * 4, o);
-      }
-    }
+    store_policy_quad<Out, C, kChannelsFirst>(out, w, pixels, q, scale, offset);
   }
 }
 
@@ -164,26 +112,6 @@ hipError_t obs_stack_typed(const uint8_t* src, const int32_t* env_ids, void* dst
 // trip of its own (1 800 waves: measured 11.5 us for this launch instead of 5).
 // The row of a frame is read while the frame's loads are in flight (the
 // policy-batch stores do not depend on it).
-struct PreKey {
-  const uint8_t* src;
-  uint8_t* pool;
-  int64_t rowbytes;
-};
-// The action of the PREVIOUS step, carried into this launch (see "carried
-// publish" below): value * !flags[e] in `dtype` to row prev_rows[e] of `pool`.
-struct PreCarry {
-  const uint8_t* src;           // (n, rowbytes); null = nothing carried
-  uint8_t* pool;
-  const uint8_t* flags;         // the replay's is_last POOL (1-byte rows): the carried step's flag is at its own row
-  int32_t rowbytes, dtype, elem, pad;
-};
-struct alignas(16) PreTable {
-  uint8_t* stepid_pool;
-  int32_t* rows_out;            // device int32[n]: the rows again, for the publish launch (may be null)
-  PreKey narrow[kPreNarrow];
-  PreCarry carry;
-  uint32_t words[1];            // rows[n] | step ids, 5 words per row | the carried step's rows[n] (7 * n words)
-};
 struct PrewriteArgs {
   const uint8_t* frames;
   void* dst;
@@ -194,62 +122,6 @@ struct PrewriteArgs {
   const PreTable* table;        // device memory
 };
 static_assert(sizeof(PrewriteArgs) == 56, "obs_stack_insert_kernel's arguments (passed one by one) fit the 14 preloaded dwords");
-
-// The narrow keys, the step id and the row for the publish launch of env n: one
-// extra workgroup per env (the first n of the grid), so that this chain of
-// dependent reads (table -> source bytes -> stores) runs beside the frame
-// workgroups instead of behind one of them.  All loads are issued before the
-// first store: three memory round trips, however many keys.
-//
-// Carried publish: when all that an insert has left after the policy is one
-// small masked key (the action) and nobody needs the masked values back, the
-// publish launch is not made at all -- the previous step's action rides in THIS
-// launch (one element per lane of the env's narrow workgroup, the same typed
-// multiply as publish_one_kernel), one dependent launch less per env step.
-__device__ __forceinline__ void prewrite_carry(const PreTable& t, const uint32_t* tab, int32_t n_envs,
-                                               int64_t n) {
-  const PreCarry c = t.carry;                    // uniform: scalar loads
-  if (!c.src) return;
-  const int64_t prev = static_cast<int32_t>(gload<uint32_t>(tab + 6 * static_cast<int64_t>(n_envs) + n));
-  const int64_t off = static_cast<int64_t>(threadIdx.x) * c.elem;
-  if (prev < 0 || off >= c.rowbytes) return;
-  // The carried step's is_last as the replay stored it (written by that step's
-  // own early-insert launch, earlier on this stream) -- not the env's output
-  // buffer, which an env with one output set has overwritten by now.
-  const bool keep = gload<uint8_t>(c.flags + prev) == 0;
-  const uint8_t* src = c.src + n * c.rowbytes + off;
-  uint8_t* pool = c.pool + prev * c.rowbytes + off;
-  put_masked_as(c.dtype, src, pool, nullptr, keep);
-}
-
-__device__ __forceinline__ void prewrite_narrow(const PrewriteArgs& a, int64_t n) {
-  const PreTable& t = *a.table;
-  const uint32_t* tab = t.words;
-  prewrite_carry(t, tab, a.n, n);
-  const int64_t row = static_cast<int32_t>(gload<uint32_t>(tab + n));
-  if (row < 0) return;
-  uint32_t sid = 0;
-  if (threadIdx.x < kStepBytes / 4)
-    sid = gload<uint32_t>(tab + a.n + n * (kStepBytes / 4) + threadIdx.x);
-  PreKey key[kPreNarrow];
-#pragma unroll
-  for (int k = 0; k < kPreNarrow; ++k) key[k] = t.narrow[k];      // uniform: scalar loads
-  uint8_t v[kPreNarrow];
-#pragma unroll
-  for (int k = 0; k < kPreNarrow; ++k) {
-    v[k] = 0;
-    if (k < a.n_narrow && static_cast<int64_t>(threadIdx.x) < key[k].rowbytes)
-      v[k] = gload<uint8_t>(key[k].src + n * key[k].rowbytes + threadIdx.x);
-  }
-#pragma unroll
-  for (int k = 0; k < kPreNarrow; ++k)
-    if (k < a.n_narrow && static_cast<int64_t>(threadIdx.x) < key[k].rowbytes)
-      gstore<uint8_t>(key[k].pool + row * key[k].rowbytes + threadIdx.x, v[k]);
-  if (t.stepid_pool && threadIdx.x < kStepBytes / 4)
-    gstore<uint32_t>(t.stepid_pool + row * kStepBytes + threadIdx.x * 4, sid);
-  if (t.rows_out && threadIdx.x == 0) t.rows_out[n] = static_cast<int32_t>(row);
-}
-static_assert(kThreads >= 256, "a narrow key (<= 256 bytes per step) is one byte per lane");
 
 // (Scalar parameters, not the struct: the kernel-argument preload only takes
 // arguments passed as scalars / pointers -- a by-value struct is fetched with
@@ -267,7 +139,11 @@ __global__ __launch_bounds__(kThreads) void obs_stack_insert_kernel(
     int32_t pixels_, int32_t frame_blocks, int32_t n_envs, int32_t n_narrow, float scale, float offset) {
   const PrewriteArgs a{frames, dst, frame_pool, pixels_, frame_blocks, scale, offset, n_envs, n_narrow, table};
   if (blockIdx.x < static_cast<uint32_t>(n_envs)) {
-    prewrite_narrow(a, blockIdx.x);
+    // (cvt, store_quad, the table and prewrite_narrow: step_device.h)
+    const int64_t n = blockIdx.x;
+    prewrite_narrow(*a.table, a.n, a.n_narrow, n, [n](const PreKey& key) {
+      return gload<uint8_t>(key.src + n * key.rowbytes + threadIdx.x);
+    });
     return;
   }
   const uint32_t id = blockIdx.x - static_cast<uint32_t>(n_envs);
@@ -289,26 +165,7 @@ __global__ __launch_bounds__(kThreads) void obs_stack_insert_kernel(
 #pragma unroll
       for (int c = 0; c < C; ++c) w[c] = frame[q * C + c];
     }
-    auto byte_at = [&w](int idx) {
-      return static_cast<uint8_t>((w[idx >> 2] >> ((idx & 3) * 8)) & 0xFFu);
-    };
-    if (kChannelsFirst) {
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        Quad<Out> o;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) o.v[p] = cvt<Out>(byte_at(p * C + c), a.scale, a.offset);
-        store_quad(out + c * pixels + q * 4, o);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < C; ++j) {
-        Quad<Out> o;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) o.v[p] = cvt<Out>(byte_at(j * 4 + p), a.scale, a.offset);
-        store_quad(out + (q * C + j) * 4, o);
-      }
-    }
+    store_policy_quad<Out, C, kChannelsFirst>(out, w, pixels, q, a.scale, a.offset);
     if (row >= 0) {
       if constexpr (C == 4) {
         __builtin_nontemporal_store(u32x4{w[0], w[1], w[2], w[3]}, reinterpret_cast<u32x4*>(pool) + q);

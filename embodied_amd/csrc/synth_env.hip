@@ -1,4 +1,8 @@
 #include "device_util.h"
+#include "step_device.h"
+#include "synth_fused.h"
+
+#include <hip/hip_ext.h>
 
 #include <algorithm>
 #include <cstring>
@@ -30,30 +34,8 @@ struct SynthArgs {
 };
 static_assert(sizeof(SynthArgs) <= 64, "synth_env_kernel's arguments (passed one by one, n from the grid) are preloaded");
 
-// Mask job: the env's launch stores `act * !reset[e]` (the policy's raw actions
-// times the flags the step itself restarts on: the Driver passes the previous
-// step's is_last as `reset`) to `out`, the Driver's masked-action buffer -- the
-// env's input as driver.py:72-75 defines it -- so that no launch of its own has
-// to make that copy.  src == null: no job.
-//
-// Where the job travels.  The preload covers 14 dwords (16 user SGPRs less the
-// two of the kernel-argument pointer; `.amdhsa_user_sgpr_kernarg_preload_length
-// 14` for synth_env_kernel) and the step's own arguments fill them: two more
-// pointers and the key's size would be fetched with s_load by EVERY wave, frame
-// workgroups included (the compiler puts the kernel-argument loads in front of
-// the first branch) -- with host-resident arguments a PCIe read in front of
-// every frame store.  So the masked form takes ONE pointer to a block in device
-// memory (written through the BAR like step.hip's PreTable) in place of the
-// three flag offsets, which move into the block: 56 bytes, all preloaded, and only
-// workgroup 0 of an env -- the one that stores the masked values and the flags --
-// reads the block.  The frame workgroups run the same instructions as before.
-struct alignas(16) SynthMaskJob {
-  const uint8_t* src;         // (n, rowbytes) raw actions
-  uint8_t* out;               // (n, rowbytes) masked actions
-  int32_t rowbytes, dtype, elem;
-  int32_t off_first, off_last, off_terminal;   // bytes from `reward` (masked form only)
-};
-static_assert(sizeof(SynthMaskJob) == kSynthJobBytes, "kernels.h states the size of the block");
+using synth_host::SynthMaskJob;      // (the blocks in device memory and their host side: synth_fused.h)
+using synth_host::SynthFusedHead;
 
 struct SynthStep {
   int32_t count;
@@ -71,15 +53,21 @@ __device__ __forceinline__ SynthStep synth_step(const SynthArgs& a, int64_t e) {
   return {count, restart, !restart && count >= length};
 }
 
+__device__ __forceinline__ uint32_t synth_salt(int64_t env0, int64_t e, int32_t count) {
+  return static_cast<uint32_t>((env0 + e) * 131 + static_cast<int64_t>(count) * 7);
+}
+// The four frame bytes from `byte0` on as one little-endian word.
+__device__ __forceinline__ uint32_t synth_word(uint32_t salt, int64_t byte0) {
+  const uint32_t x = salt + static_cast<uint32_t>(byte0);
+  return (x & 0xFF) | (((x + 1) & 0xFF) << 8) | (((x + 2) & 0xFF) << 16) | (((x + 3) & 0xFF) << 24);
+}
+
 // byte i of the frame = (salt + i) & 0xFF, written 16 bytes per lane.
 __device__ __forceinline__ void synth_frame(const SynthArgs& a, int64_t e, int32_t count, uint32_t blocks) {
-  const uint32_t salt = static_cast<uint32_t>((a.env0 + e) * 131 + static_cast<int64_t>(count) * 7);
+  const uint32_t salt = synth_salt(a.env0, e, count);
   u32x4* out = reinterpret_cast<u32x4*>(a.image + e * a.frame_bytes);
   const int64_t vecs = a.frame_bytes >> 4;
-  auto word = [salt](int64_t byte0) {
-    const uint32_t x = salt + static_cast<uint32_t>(byte0);
-    return (x & 0xFF) | (((x + 1) & 0xFF) << 8) | (((x + 2) & 0xFF) << 16) | (((x + 3) & 0xFF) << 24);
-  };
+  auto word = [salt](int64_t byte0) { return synth_word(salt, byte0); };
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; i < vecs;
        i += static_cast<int64_t>(blocks) * kThreads)
     __builtin_nontemporal_store(
@@ -171,11 +159,78 @@ __global__ __launch_bounds__(kThreads) void synth_env_far_kernel(
   }
 }
 
+// ------------------------------------------- step + obs stack + early insert --
+//
+// The masked step above writes every frame to the env's image buffer; one kernel
+// boundary later obs_stack_insert_kernel (step.hip) reads the same bytes back to
+// cast them into the policy batch and copy them into the replay's pool.  Nothing
+// runs in between but the host, and the lane that generates 16 bytes of a frame
+// holds them in registers: here it stores all three copies itself.  No workgroup
+// depends on another, one boundary and the re-read of every frame are gone.
+//
+// The device block: synth_fused.h SynthFusedHead, then the early insert's table.
+static_assert(kSynthFusedHeadBytes % alignof(PreTable) == 0, "the early insert's table follows the head");
+
+// Grid as obs_stack_insert_kernel's (one dimension: the n narrow workgroups
+// first, then the frame blocks env by env -- see its comment on XCD placement),
+// frame slicing as obs_stack_insert_typed's: min(ceil(quads / 256), 32) blocks
+// per env, so one lane owns the same 16 bytes for all three stores.  4 channels.
+// 56 bytes of arguments = the 14 preloaded dwords; `counters_in` is the
+// generation this step reads.
+template <typename Out, bool kChannelsFirst>
+__global__ __launch_bounds__(kThreads) void synth_env_fused_kernel(
+    const int32_t* __restrict__ counters_in, const uint8_t* __restrict__ reset, uint8_t* image, void* dst,
+    uint8_t* frame_pool, const SynthFusedHead* __restrict__ blk, int32_t frame_bytes, int32_t n_envs) {
+  const PreTable& t = *reinterpret_cast<const PreTable*>(blk + 1);
+  if (blockIdx.x < static_cast<uint32_t>(n_envs)) {
+    const int64_t e = blockIdx.x;
+    const SynthFusedHead h = *blk;                 // uniform: scalar loads
+    const SynthArgs a{h.counters, reset, image, h.reward, 0, 0, 0, frame_bytes, h.env0, h.len_turn & 0x7FFFFFFF,
+                      static_cast<int32_t>(static_cast<uint32_t>(n_envs) << 1 | (static_cast<uint32_t>(h.len_turn) >> 31))};
+    const SynthStep s = synth_step(a, e);
+    synth_masked_action(h.job, reset, e);
+    uint8_t* flags = reinterpret_cast<uint8_t*>(h.reward);
+    const uint8_t* first = flags + h.job.off_first;
+    if (threadIdx.x == 0)
+      synth_bookkeeping(a, e, s, flags + h.job.off_first, flags + h.job.off_last, flags + h.job.off_terminal);
+    // The pool rows of reward and flags from the registers bookkeeping stored.
+    const uint32_t reward_bits = __float_as_uint(s.restart ? 0.f : static_cast<float>(s.count % 7));
+    const uint8_t* reward_src = reinterpret_cast<const uint8_t*>(h.reward);
+    prewrite_narrow(t, n_envs, h.n_narrow, e, [&](const PreKey& key) -> uint8_t {
+      if (key.src == reward_src) return static_cast<uint8_t>(reward_bits >> ((threadIdx.x & 3) * 8));
+      if (key.src == first) return s.restart ? 1 : 0;
+      return s.done ? 1 : 0;                       // is_last, is_terminal
+    });
+    return;
+  }
+  const uint32_t quads = static_cast<uint32_t>(frame_bytes) >> 4;
+  const uint32_t frame_blocks = min((quads + kThreads - 1) / kThreads, 32u);
+  const uint32_t id = blockIdx.x - static_cast<uint32_t>(n_envs);
+  const int64_t e = id / frame_blocks;
+  const uint32_t block = id - static_cast<uint32_t>(e) * frame_blocks;
+  const int64_t row = static_cast<int32_t>(gload<uint32_t>(t.words + e));    // used by the pool store only
+  const int32_t env0 = blk->env0;
+  const float scale = blk->scale, offset = blk->offset;
+  const bool restart = reset[e] != 0 || counters_in[2 * e + 1] != 0;
+  const int32_t count = restart ? 0 : counters_in[2 * e] + 1;
+  const uint32_t salt = synth_salt(env0, e, count);
+  const int64_t pixels = static_cast<uint32_t>(frame_bytes) >> 2;
+  u32x4* img = reinterpret_cast<u32x4*>(image + e * frame_bytes);
+  u32x4* pool = reinterpret_cast<u32x4*>(frame_pool + row * frame_bytes);
+  Out* out = static_cast<Out*>(dst) + e * pixels * 4;
+  for (uint32_t q = block * kThreads + threadIdx.x; q < quads; q += frame_blocks * kThreads) {
+    const int64_t b = static_cast<int64_t>(q) * 16;
+    const uint32_t w[4] = {synth_word(salt, b), synth_word(salt, b + 4), synth_word(salt, b + 8),
+                           synth_word(salt, b + 12)};
+    __builtin_nontemporal_store(u32x4{w[0], w[1], w[2], w[3]}, img + q);
+    store_policy_quad<Out, 4, kChannelsFirst>(out, w, pixels, q, scale, offset);
+    if (row >= 0) __builtin_nontemporal_store(u32x4{w[0], w[1], w[2], w[3]}, pool + q);
+  }
+}
+
 bool synth_args(SynthArgs* a, uint8_t* image, float* reward, int64_t n, int64_t frame_bytes, int64_t env0,
                 int64_t episode_len, const uint8_t* reset, int32_t* counters, int turn, dim3* grid) {
-  if (frame_bytes % 16 != 0 || reinterpret_cast<uint64_t>(image) % 16 != 0 || n > (1 << 29) ||
-      frame_bytes > INT32_MAX || env0 > INT32_MAX || episode_len > INT32_MAX)
-    return false;
+  if (!synth_host::shape_ok(image, n, frame_bytes, env0, episode_len)) return false;
   a->counters = counters;
   a->reset = reset;
   a->image = image;
@@ -193,18 +248,10 @@ bool synth_args(SynthArgs* a, uint8_t* image, float* reward, int64_t n, int64_t 
   return true;
 }
 
-// The flag buffers as 32-bit offsets from `reward`; false when one does not fit.
+using synth_host::offsets;
 bool synth_offsets(const float* reward, const uint8_t* is_first, const uint8_t* is_last,
                    const uint8_t* is_terminal, int32_t* of, int32_t* ol, int32_t* ot) {
-  const int64_t base = reinterpret_cast<int64_t>(reward);
-  const int64_t f = reinterpret_cast<int64_t>(is_first) - base, l = reinterpret_cast<int64_t>(is_last) - base,
-                t = reinterpret_cast<int64_t>(is_terminal) - base;
-  auto fits = [](int64_t x) { return x >= INT32_MIN && x <= INT32_MAX; };
-  if (!fits(f) || !fits(l) || !fits(t)) return false;
-  *of = static_cast<int32_t>(f);
-  *ol = static_cast<int32_t>(l);
-  *ot = static_cast<int32_t>(t);
-  return true;
+  return offsets(reward, is_first, is_last, is_terminal, of, ol, ot);
 }
 
 int32_t len_turn_word(const SynthArgs& a, int turn) {
@@ -266,6 +313,49 @@ hipError_t launch_synth_env_masked(uint8_t* image, float* reward, uint8_t* is_fi
     hipLaunchKernelGGL(synth_env_far_kernel, grid, dim3(kThreads), 0, stream, a, is_first, is_last,
                        is_terminal, j);
   }
+  return hipGetLastError();
+}
+
+const char* synth_fused_refusal(const SynthStepArgs& env, const PrewritePlan& plan) {
+  return synth_host::fused_refusal(env, plan);
+}
+
+size_t synth_fused_block_bytes(int64_t n) { return synth_host::fused_block_bytes(n); }
+
+void synth_fused_fill(void* dst, const SynthStepArgs& env, const PrewritePlan& plan, const int32_t* rows,
+                      const uint8_t* stepids) {
+  synth_host::fused_fill(dst, env, dtype_size(env.dtype), plan, rows, stepids);
+}
+
+// (The caller has asked synth_fused_refusal: replay_early_insert does, before it touches its handle.)
+hipError_t launch_synth_env_fused(const SynthStepArgs& env, const PrewritePlan& plan, const void* block_dev,
+                                  hipStream_t stream, hipEvent_t stop) {
+  if (!block_dev || plan.channels != 4 || plan.n != env.n) return hipErrorInvalidValue;
+  const uint32_t quads = static_cast<uint32_t>(env.frame_bytes >> 4);
+  const uint32_t frame_blocks = std::min<uint32_t>((quads + kThreads - 1) / kThreads, 32u);
+  const dim3 grid(static_cast<uint32_t>(env.n) * (frame_blocks + 1));
+  const int32_t* counters_in = env.counters + (env.turn & 1) * 2 * env.n;
+  const bool cf = plan.layout == kLayoutChannelsFirst;
+#define EMB_FUSED_ARGS counters_in, env.reset, env.image, plan.dst, plan.frame_pool,                   \
+                       static_cast<const SynthFusedHead*>(block_dev), static_cast<int32_t>(env.frame_bytes), \
+                       static_cast<int32_t>(env.n)
+#define EMB_FUSED(Out)                                                                                  \
+  if (cf && stop) hipExtLaunchKernelGGL((synth_env_fused_kernel<Out, true>), grid, dim3(kThreads), 0,  \
+                                        stream, nullptr, stop, 0, EMB_FUSED_ARGS);                      \
+  else if (cf) hipLaunchKernelGGL((synth_env_fused_kernel<Out, true>), grid, dim3(kThreads), 0, stream, \
+                                  EMB_FUSED_ARGS);                                                      \
+  else if (stop) hipExtLaunchKernelGGL((synth_env_fused_kernel<Out, false>), grid, dim3(kThreads), 0,  \
+                                       stream, nullptr, stop, 0, EMB_FUSED_ARGS);                       \
+  else hipLaunchKernelGGL((synth_env_fused_kernel<Out, false>), grid, dim3(kThreads), 0, stream,       \
+                          EMB_FUSED_ARGS);
+  switch (plan.out_dtype) {
+    case kU8: EMB_FUSED(uint8_t) break;
+    case kF16: EMB_FUSED(__half) break;
+    case kBF16: EMB_FUSED(__hip_bfloat16) break;
+    default: EMB_FUSED(float) break;
+  }
+#undef EMB_FUSED
+#undef EMB_FUSED_ARGS
   return hipGetLastError();
 }
 

@@ -5,6 +5,8 @@ This is the benchmark/test input of SURVEY.md 8d: real simulators are CPU code
 outside the hot path.  `host_step` restates the same generator in numpy so the
 frames can be verified and a CPU baseline can run on identical data.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -26,6 +28,10 @@ class SyntheticBatchEnv:
     # unmasked)` stores unmasked * ~reset into acts' tensors, in one launch with
     # the frames (emb_synth_env_step_masked).  One action key, as its act_space.
     self.masks_actions_in_step = True
+    # ... and, with an output ring, may write the policy batch and the replay's
+    # pool rows of the step it produces as well (base.BatchEnv): `peek_fused` /
+    # `commit_fused`, emb_synth_env_step_fused.
+    self.stacks_obs_in_step = ring > 0
     self.shape = tuple(shape)
     self.frame_bytes = int(np.prod(shape))
     assert self.frame_bytes % 16 == 0
@@ -47,6 +53,8 @@ class SyntheticBatchEnv:
     self._ring_ptrs = [tuple(v.data_ptr() for v in obs.values()) for obs in self.ring]
     self._counters_ptr = self.counters.data_ptr()
     self._calls = {}
+    self._fused = {}
+    self._reset_keep = None
     self.turn = 0
 
   def __len__(self):
@@ -122,7 +130,9 @@ class SyntheticBatchEnv:
       # the previous is_last): the workgroups that share an env's frame would
       # read it before and after workgroup 0's store -- step on a copy (the mask
       # job reads the same copy: the flags the env logic uses).
-      reset = reset.clone()
+      kept = self._reset_keep
+      reset = kept[1] if kept is not None and kept[0] is reset else reset.clone()
+      self._reset_keep = None
       reset_ptr = reset.data_ptr()
       turn = -1                   # (a fresh copy per step: nothing to remember)
     args = (image, reward, is_first, is_last, is_terminal, n, self.frame_bytes, self.env0,
@@ -135,6 +145,50 @@ class SyntheticBatchEnv:
       self._calls[(turn, self.generation)] = (reset, args)
     self.generation ^= 1
     return obs
+
+
+  def peek_fused(self, acts, unmasked):
+    """(obs, address of the emb_synth_step_t, arm) of the step that `step(acts,
+    unmasked)` would make now -- the ring's next output set and the launch's
+    arguments -- without making it, or None (no ring, more than one action key).
+    `arm`: None, or what to call right before the launch is asked for.
+    Whoever launches it (Replay.step_fused) calls `commit_fused` afterwards."""
+    if not self.ring or len(unmasked) != 1:
+      return None
+    (name, raw), = unmasked.items()
+    out, reset = acts[name], acts['reset']
+    n, dev, turn = self.n, self.device, self.turn
+    assert (raw.dtype == out.dtype and raw.shape == out.shape and raw.shape[0] == n
+            and raw.is_contiguous() and out.is_contiguous() and raw.device == out.device == dev), name
+    cached = self._fused.get((turn, self.generation))
+    if cached is None or cached[0] is not reset or cached[1] is not out:
+      image, reward, is_first, is_last, is_terminal = self._ring_ptrs[turn]
+      # (`reset` may be a flag buffer this very step writes, ring=1: see `step`)
+      aliased = reset.data_ptr() in (is_first, is_last, is_terminal)
+      block = _lib.SynthStep(
+          image, reward, is_first, is_last, is_terminal, n, self.frame_bytes, self.env0, self.episode_len,
+          reset.data_ptr(), self._counters_ptr, 0, out.data_ptr(), raw.numel() // n * raw.element_size(),
+          self.generation, _DTYPE_CODE[raw.dtype])
+      cached = self._fused[(turn, self.generation)] = (reset, out, block, C.addressof(block), aliased)
+    cached[2].act = raw.data_ptr()
+    self._arming = (cached[2], reset) if cached[4] else None
+    return dict(self.ring[turn]), cached[3], (self._arm if cached[4] else None)
+
+  def _arm(self):
+    """`reset` is a flag buffer the step about to be launched writes: it steps on
+    a copy (see `step`), made only now that the launch is all but certain -- and
+    kept for `step`, should the launch be refused after all."""
+    block, reset = self._arming
+    copy = reset.clone()
+    self._reset_keep = (reset, copy)
+    block.reset = copy.data_ptr()
+
+  def commit_fused(self):
+    """The step `peek_fused` described has been launched."""
+    self.turn = (self.turn + 1) % len(self.ring)
+    self.generation ^= 1
+    if self._reset_keep is not None:
+      self._reset_keep = (None, self._reset_keep[1])     # used up (kept alive for the launch)
 
 
 _DTYPE_CODE = {

@@ -22,7 +22,13 @@ def obs_stack(frames, env_ids=None, layout='channels_first', dtype=torch.uint8,
   (n, C, H, W) [channels_first] or (n, H, W, C) [same] as `dtype`, values
   `x * scale + offset` for float outputs; batch row j is env `env_ids[j]`.
   `out`: a contiguous tensor of that shape and dtype to write into (an agent
-  that owns its input staging saves the allocation, ~2.5 us of host time)."""
+  that owns its input staging saves the allocation, ~2.5 us of host time).
+
+  A staging buffer handed in for a frame tensor of a device env that
+  `stacks_obs_in_step` may be written by that env's NEXT step launch on the same
+  ring slot (emb_synth_env_step_fused builds the policy batch while it generates
+  the frames): this call then returns `out` without a launch.  Do not keep other
+  data in it across env steps."""
   if env_ids is None and out is not None and type(frames) is torch.Tensor:
     # The same frame tensor into the same staging tensor with the same options as
     # before (a vector env's output ring, an agent's staging buffers): both
@@ -52,6 +58,7 @@ def obs_stack(frames, env_ids=None, layout='channels_first', dtype=torch.uint8,
   n = total if ids is None else len(ids)
   first = layout == 'channels_first'
   shape = (n, c, h, w) if first else (n, h, w, c)
+  given = out is not None        # (a batch allocated here is the caller's alone: never written again)
   if out is None:
     out = _lib.empty(shape, dtype, frames.device)
   elif not (out.shape == shape and out.dtype is dtype and out.is_contiguous()
@@ -60,7 +67,7 @@ def obs_stack(frames, env_ids=None, layout='channels_first', dtype=torch.uint8,
   if out.numel() == 0:
     return out                       # no envs / empty frames: nothing to launch
   if ids is None and type(frames) is torch.Tensor:
-    frames._emb_stack = (out, layout, dtype, float(scale), float(offset), n, h * w, c, first)
+    frames._emb_stack = (out, layout, dtype, float(scale), float(offset), n, h * w, c, first, given)
   tag = getattr(frames, '_emb_offer', None)
   if tag is not None and ids is None:
     # A Driver offered this step's observations to its Replay (Replay.offer):

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports (157 functions). */
+ * it exports (158 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -1294,6 +1294,40 @@ int32_t emb_synth_env_step_masked(void* image, void* reward, void* is_first, voi
 /* 1 if an action key of this row size and dtype can be masked inside a device
  * env's step launch (and carried by the replay), else 0.                        */
 int32_t emb_env_mask_supported(int64_t row_bytes, int32_t dtype);
+/* The masked step's arguments as one block (emb_synth_env_step_fused).          */
+typedef struct {
+  void *image, *reward, *is_first, *is_last, *is_terminal;
+  int64_t n, frame_bytes, env0, episode_len;
+  const void* reset;
+  void* counters;
+  const void* act;
+  void* masked_out;
+  int64_t row_bytes;
+  int32_t turn, dtype;
+} emb_synth_step_t;
+/* The masked step AND the early insert of the step it produces
+ * (emb_replay_obs_stack_insert with frames = env->image) in ONE launch: the
+ * workgroup that generates a frame slice stores it to the env's image buffer,
+ * to its pool row and, cast as `spec` says, to the policy batch `dst`; reward
+ * and flags go to the env's buffers and to their pool rows from registers; the
+ * carried publish rides along.  An env step is one launch instead of two.
+ * The other arguments are emb_replay_obs_stack_insert's; `src[k]` of an
+ * observation key is the env's buffer for it.
+ *   *token_out != 0: launched; go on with emb_replay_publish(token) as after
+ *     emb_replay_obs_stack_insert.  The policy batch is in `dst`.
+ *   *token_out == 0 (and EMB_OK): nothing was launched and neither handle nor
+ *     env state changed -- the rows of the step are not predicted (the helper
+ *     thread would have to be waited for) or EMB_STEP_FUSED=0 is set.  Make the
+ *     two launches (emb_synth_env_step_masked, emb_replay_obs_stack_insert).
+ *   EMB_ERR_INVALID, nothing launched: the launch cannot take this step at all
+ *     -- the plan fails the early insert's own checks, frames are not 4-channel
+ *     uint8 in env->image, a narrow key's source is not one of the env's four
+ *     output buffers (reward as 4-byte rows, the flags as 1-byte rows), the flag
+ *     buffers are not within 32-bit offsets of `reward`, or the action key is
+ *     not one emb_env_mask_supported accepts.  Two launches, as before.        */
+int32_t emb_synth_env_step_fused(emb_replay_t* rep, int64_t n, const int64_t* workers, int32_t frame_key,
+                                 const emb_synth_step_t* env, const emb_obs_spec_t* spec, void* dst,
+                                 const void* const* src, void* stream, uint64_t* token_out);
 
 /* ---- direct xGMI schedule (round 5) ----------------------------------------
  * The two collectives of a train step -- the gradient all-reduce
