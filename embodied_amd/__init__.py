@@ -42,7 +42,7 @@ from .outs import Normal, normal_policy_loss, philox_normal, normal_policy_launc
 from . import nets
 from .nets import NormAct, norm_act, gru_gate, norm_act_launches, gru_gate_launches
 from . import optim
-from .optim import LaProp, Adam, optimizer_launches
+from .optim import LaProp, Adam, SlowModel, optimizer_launches
 from .utils import Counter, LocalClock
 from .distributed import GlobalClock
 # `embodied.clock.*` by name (embodied/core/__init__.py:4-5,11): the two clocks and

@@ -256,6 +256,10 @@ SIGNATURES = {
     'emb_optim_adam_update': [p, p, i64, p, f32, f32, f32, f32, f32, f32, f32, f32, f32, f32, p],
     'emb_optim_metrics': [p, i64, i64, p, p],
     'emb_optim_launches': [p],
+    'emb_slow_table': [p, p, i64, p, p, i64, p, p],
+    'emb_slow_update': [p, p, i64, f32, f32, p],
+    'emb_optim_update_slow': [p, p, i64, p, f32, f32, f32, f32, f32, f32, f32, f32, f32, f32, f32, i32, p, f32, f32, p],
+    'emb_optim_adam_update_slow': [p, p, i64, p, f32, f32, f32, f32, f32, f32, f32, f32, f32, f32, p, f32, f32, p],
     'emb_norm_act': [p, p, p, i32, i64, i64, i32, i32, f32, p, p],
     'emb_norm_act_grad': [p, p, p, p, i32, i64, i64, i32, i32, f32, p, p, p, p, i64, p],
     'emb_norm_act_launches': [p],

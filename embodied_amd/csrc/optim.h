@@ -103,6 +103,74 @@ inline const char* optim_plan(const int64_t* addrs, const int64_t* counts, const
   return nullptr;
 }
 
+// ---- the slow (EMA) copy of a set of tensors, embodied/jax/utils.py:94-127:
+// dst = mix * src + (1 - mix) * dst over every tensor in one launch, on the same
+// kind of chunk map.
+
+// One per tensor, read by every workgroup that holds one of its chunks.
+struct SlowTensor {
+  uint64_t dst, src;       // device addresses, float32: the slow copy and what it follows
+  int32_t n;               // elements, 0 .. 2^31 - 1
+  int32_t first_chunk;     // index of the tensor's first chunk
+  int32_t flags;           // kOptimVector or 0
+  int32_t head;            // 0 .. 3 scalar elements in front of a chunk's first aligned vector
+};
+static_assert(sizeof(SlowTensor) == 32, "the table is read as 32-byte records");
+
+// addrs (tensors, 2) = dst, src of every tensor; counts (tensors).  The
+// conventions of optim_plan: writes the number of chunks and, where given, the
+// table and the chunk map; a tensor of 0 elements has a record and no chunk;
+// returns null, or what is wrong, and then has written nothing.
+//
+// A tensor takes the vector path when, from the first 16-byte boundary of dst
+// on, src is aligned too; otherwise every access of that tensor is scalar.
+inline const char* slow_plan(const int64_t* addrs, const int64_t* counts, int64_t tensors, SlowTensor* table,
+                             OptimChunk* chunks, int64_t chunk_capacity, int64_t* n_chunks) {
+  if (tensors < 0 || tensors > INT32_MAX) return "slow_table: the number of tensors is outside 0 .. 2^31 - 1";
+  if (tensors > 0 && (!addrs || !counts)) return "slow_table: a pointer is null";
+  int64_t total = 0;
+  for (int64_t i = 0; i < tensors; ++i) {
+    if (counts[i] < 0 || counts[i] > INT32_MAX) return "slow_table: a tensor of more than 2^31 - 1 elements";
+    const int64_t* a = addrs + 2 * i;
+    if (counts[i] > 0) {
+      if (!a[0] || !a[1]) return "slow_table: a null address";
+      if ((a[0] | a[1]) & 3) return "slow_table: an address that is not aligned to its element";
+      if (a[0] == a[1]) return "slow_table: dst and src are the same tensor";
+    }
+    total += optim_chunks_of(counts[i]);
+  }
+  if (total > INT32_MAX) return "slow_table: more than 2^31 - 1 chunks";
+  if (chunks && chunk_capacity < total) return "slow_table: the chunk map is too small";
+  if (n_chunks) *n_chunks = total;
+  int64_t next = 0;
+  for (int64_t i = 0; i < tensors; ++i) {
+    const int64_t* a = addrs + 2 * i;
+    const int64_t n = counts[i];
+    if (table) {
+      SlowTensor t{};
+      t.dst = static_cast<uint64_t>(a[0]);
+      t.src = static_cast<uint64_t>(a[1]);
+      t.n = static_cast<int32_t>(n);
+      t.first_chunk = static_cast<int32_t>(next);
+      if (n > 0) {
+        const uint64_t head = ((16 - (t.dst & 15)) & 15) / 4;
+        if (((t.src + 4 * head) & 15) == 0) {
+          t.flags = kOptimVector;
+          t.head = static_cast<int32_t>(head);
+        }
+      }
+      table[i] = t;
+    }
+    for (int64_t off = 0; off < n; off += kOptimChunk, ++next) {
+      if (chunks) {
+        chunks[next].tensor = static_cast<int32_t>(i);
+        chunks[next].offset = static_cast<int32_t>(off);
+      }
+    }
+  }
+  return nullptr;
+}
+
 }  // namespace emb
 
 #ifndef EMB_OPTIM_HOST_ONLY
@@ -151,7 +219,21 @@ hipError_t launch_optim_adam_update(const OptimTensor* table, const OptimChunk* 
 // nets.py:120-124) from the partials, one workgroup, a fixed order.
 hipError_t launch_optim_metrics(const float* partials, int64_t n_chunks, int64_t count, float* out, hipStream_t stream);
 
-// Kernel launches the five launchers have issued in this process.
+// dst = mix * src + omm * dst over every tensor of a slow_plan table, one launch
+// (utils.py:117-119); two rounded products and one rounded sum per element.
+hipError_t launch_slow_update(const SlowTensor* table, const OptimChunk* chunks, int64_t n_chunks, float mix, float omm,
+                              hipStream_t stream);
+// launch_optim_update / launch_optim_adam_update that also write the slow copy
+// while p_new is in registers: `slow` holds one device address per table entry,
+// 0 where a tensor has none; d = mix * p_new + omm * d at the same element index.
+hipError_t launch_optim_update_slow(const OptimTensor* table, const OptimChunk* chunks, int64_t n_chunks,
+                                    float* partials, const OptimStep& step, const uint64_t* slow, float mix, float omm,
+                                    hipStream_t stream);
+hipError_t launch_optim_adam_update_slow(const OptimTensor* table, const OptimChunk* chunks, int64_t n_chunks,
+                                         float* partials, const AdamStep& step, const uint64_t* slow, float mix,
+                                         float omm, hipStream_t stream);
+
+// Kernel launches the launchers above have issued in this process.
 int64_t optim_launches();
 
 }  // namespace emb

@@ -22,6 +22,11 @@
 // update launch sums the partials of ALL chunks, once per workgroup, for the one
 // global norm.
 //
+// The slow (EMA) copy of a set of tensors (embodied/jax/utils.py:94-127,
+// dreamerv3/agent.py:142) is one more pass over such a chunk map: a launch of its
+// own (slow_update_kernel), or no launch at all -- the SLOW instantiations of the
+// two update kernels write it from the p_new they still hold in registers.
+//
 // One workgroup per chunk of kOptimChunk elements of one tensor (grid-stride past
 // kMaxBlocks), 16-byte loads and stores from the chunk's first aligned element
 // on and scalar ones at its ragged ends (optim.h: optim_plan decides per tensor).
@@ -91,7 +96,8 @@ struct Span {
   int32_t lo, first, nvec, tail, hi;
 };
 
-__device__ __forceinline__ Span span_of(const OptimTensor& t, int32_t offset) {
+template <class Tensor>                            // OptimTensor or SlowTensor
+__device__ __forceinline__ Span span_of(const Tensor& t, int32_t offset) {
   Span s;
   s.lo = offset;
   s.hi = min(t.n - offset, kOptimChunk) + offset;
@@ -107,8 +113,9 @@ __device__ __forceinline__ Span span_of(const OptimTensor& t, int32_t offset) {
   return s;
 }
 
-__device__ __forceinline__ OptimTensor tensor_of(const OptimTensor* table, const OptimChunk* chunks, int32_t chunk,
-                                                 int32_t& tensor, int32_t& offset) {
+template <class Tensor>
+__device__ __forceinline__ Tensor tensor_of(const Tensor* table, const OptimChunk* chunks, int32_t chunk,
+                                            int32_t& tensor, int32_t& offset) {
   // the same in every lane: read through scalar registers
   tensor = __builtin_amdgcn_readfirstlane(chunks[chunk].tensor);
   offset = __builtin_amdgcn_readfirstlane(chunks[chunk].offset);
@@ -187,9 +194,45 @@ __device__ __forceinline__ void update_one(float g, float& p, float& nu, float& 
   pnsq = pnsq + p * p;
 }
 
-template <bool BF16>
+// The slow copy of one element (utils.py:118): two products and one sum.
+__device__ __forceinline__ float slow_one(float src, float dst, float mix, float omm) { return mix * src + omm * dst; }
+
+// The four elements of a slow copy at d + i: one 16-byte access where `d + i` is
+// aligned (VECTOR), else four scalar ones.  Read with the step's other loads,
+// written from p_new right after p was.
+template <bool VECTOR>
+__device__ __forceinline__ float4 slow_load4(const float* d, int32_t i) {
+  if constexpr (VECTOR) return *reinterpret_cast<const float4*>(d + i);
+  else return make_float4(d[i], d[i + 1], d[i + 2], d[i + 3]);
+}
+
+template <bool VECTOR>
+__device__ __forceinline__ void slow_store4(float* d, int32_t i, const float4& pv, float4 dv, float mix, float omm) {
+  dv.x = slow_one(pv.x, dv.x, mix, omm);
+  dv.y = slow_one(pv.y, dv.y, mix, omm);
+  dv.z = slow_one(pv.z, dv.z, mix, omm);
+  dv.w = slow_one(pv.w, dv.w, mix, omm);
+  if constexpr (VECTOR) {
+    *reinterpret_cast<float4*>(d + i) = dv;
+  } else {
+    d[i] = dv.x, d[i + 1] = dv.y, d[i + 2] = dv.z, d[i + 3] = dv.w;
+  }
+}
+
+// Whether the slow copy at address `d` of a tensor on the vector path takes
+// 16-byte accesses too: aligned at element `head`, hence at the first vector of
+// every chunk.  The same in every lane.
+__device__ __forceinline__ bool slow_aligned(const OptimTensor& t, uint64_t d) {
+  return __builtin_amdgcn_readfirstlane(static_cast<int32_t>((d + 4u * static_cast<uint32_t>(t.head)) & 15u)) == 0;
+}
+
+// SLOW: `d` is the tensor's slow copy, written from p_new at the same index;
+// SLOW_VECTOR: in 16-byte accesses on the vector path.  Without SLOW, `d`, `mix`
+// and `omm` are not looked at.
+template <bool BF16, bool SLOW = false, bool SLOW_VECTOR = false>
 __device__ __forceinline__ void update_chunk(const OptimTensor& t, const Span& s, float scale, const OptimStep& step,
-                                             float& usq, float& pnsq) {
+                                             float& usq, float& pnsq, float* d = nullptr, float mix = 0.f,
+                                             float omm = 0.f) {
   float* p = reinterpret_cast<float*>(t.p);
   float* nu = reinterpret_cast<float*>(t.nu);
   float* mu = reinterpret_cast<float*>(t.mu);
@@ -200,19 +243,26 @@ __device__ __forceinline__ void update_chunk(const OptimTensor& t, const Span& s
     float pv = p[i], nv = nu[i], mv = mu[i];
     update_one(grad_at<BF16>(g, i), pv, nv, mv, scale, decay, step, usq, pnsq);
     p[i] = pv, nu[i] = nv, mu[i] = mv;
+    if constexpr (SLOW) d[i] = slow_one(pv, d[i], mix, omm);
   }
-#pragma unroll 2
+  // two steps in flight; with the slow copy's registers on top that costs a wave
+  // per SIMD (85 VGPRs against 76), so the SLOW instantiations take one
+  constexpr int kSteps = SLOW ? 1 : 2;
+#pragma unroll kSteps
   for (int32_t v = tid; v < s.nvec; v += kThreads) {
     const int32_t i = s.first + 4 * v;
     const float4 gv = grad4_at<BF16>(g, i);
     float4 pv = *reinterpret_cast<const float4*>(p + i);
     float4 nv = *reinterpret_cast<const float4*>(nu + i);
     float4 mv = *reinterpret_cast<const float4*>(mu + i);
+    [[maybe_unused]] float4 dv;
+    if constexpr (SLOW) dv = slow_load4<SLOW_VECTOR>(d, i);
     update_one(gv.x, pv.x, nv.x, mv.x, scale, decay, step, usq, pnsq);
     update_one(gv.y, pv.y, nv.y, mv.y, scale, decay, step, usq, pnsq);
     update_one(gv.z, pv.z, nv.z, mv.z, scale, decay, step, usq, pnsq);
     update_one(gv.w, pv.w, nv.w, mv.w, scale, decay, step, usq, pnsq);
     *reinterpret_cast<float4*>(p + i) = pv;
+    if constexpr (SLOW) slow_store4<SLOW_VECTOR>(d, i, pv, dv, mix, omm);
     *reinterpret_cast<float4*>(nu + i) = nv;
     *reinterpret_cast<float4*>(mu + i) = mv;
   }
@@ -220,12 +270,18 @@ __device__ __forceinline__ void update_chunk(const OptimTensor& t, const Span& s
     float pv = p[i], nv = nu[i], mv = mu[i];
     update_one(grad_at<BF16>(g, i), pv, nv, mv, scale, decay, step, usq, pnsq);
     p[i] = pv, nu[i] = nv, mu[i] = mv;
+    if constexpr (SLOW) d[i] = slow_one(pv, d[i], mix, omm);
   }
 }
 
+// SLOW: slow[tensor] is the address of that tensor's slow copy, 0 for none; it,
+// `mix` and `omm` are read by the SLOW instantiation only.
+template <bool SLOW>
 __global__ __launch_bounds__(kThreads) void optim_update_kernel(const OptimTensor* __restrict__ table,
                                                                 const OptimChunk* __restrict__ chunks, int32_t n_chunks,
-                                                                float* __restrict__ partials, const OptimStep step) {
+                                                                float* __restrict__ partials, const OptimStep step,
+                                                                const uint64_t* __restrict__ slow, float mix,
+                                                                float omm) {
   __shared__ float lds[2][kThreads / kWave];
   const float* gsq_of = partials;
   const float* psq_of = partials + n_chunks;
@@ -251,7 +307,18 @@ __global__ __launch_bounds__(kThreads) void optim_update_kernel(const OptimTenso
     }
     const Span s = span_of(t, offset);
     float usq = 0.f, pnsq = 0.f;
-    if (t.flags & kOptimBf16) update_chunk<true>(t, s, scale, step, usq, pnsq);
+    uint64_t d = 0;
+    if constexpr (SLOW) d = slow[tensor];           // `tensor` is the same in every lane
+    if (SLOW && d) {
+      float* to = reinterpret_cast<float*>(d);
+      if (slow_aligned(t, d)) {
+        if (t.flags & kOptimBf16) update_chunk<true, true, true>(t, s, scale, step, usq, pnsq, to, mix, omm);
+        else update_chunk<false, true, true>(t, s, scale, step, usq, pnsq, to, mix, omm);
+      } else {
+        if (t.flags & kOptimBf16) update_chunk<true, true, false>(t, s, scale, step, usq, pnsq, to, mix, omm);
+        else update_chunk<false, true, false>(t, s, scale, step, usq, pnsq, to, mix, omm);
+      }
+    } else if (t.flags & kOptimBf16) update_chunk<true>(t, s, scale, step, usq, pnsq);
     else update_chunk<false>(t, s, scale, step, usq, pnsq);
     block_sum2<kThreads>(usq, pnsq, lds);
     if (threadIdx.x == 0) {
@@ -280,9 +347,10 @@ __device__ __forceinline__ void adam_one(float g, float& p, float& nu, float& mu
   pnsq = pnsq + p * p;
 }
 
-template <bool BF16>
+template <bool BF16, bool SLOW = false, bool SLOW_VECTOR = false>
 __device__ __forceinline__ void adam_chunk(const OptimTensor& t, const Span& s, bool clipped, float gnorm,
-                                           const AdamStep& step, float& usq, float& pnsq) {
+                                           const AdamStep& step, float& usq, float& pnsq, float* d = nullptr,
+                                           float mix = 0.f, float omm = 0.f) {
   float* p = reinterpret_cast<float*>(t.p);
   float* nu = reinterpret_cast<float*>(t.nu);
   float* mu = reinterpret_cast<float*>(t.mu);
@@ -293,6 +361,7 @@ __device__ __forceinline__ void adam_chunk(const OptimTensor& t, const Span& s, 
     float pv = p[i], nv = nu[i], mv = mu[i];
     adam_one(grad_at<BF16>(g, i), pv, nv, mv, clipped, gnorm, decay, step, usq, pnsq);
     p[i] = pv, nu[i] = nv, mu[i] = mv;
+    if constexpr (SLOW) d[i] = slow_one(pv, d[i], mix, omm);
   }
 #pragma unroll 2
   for (int32_t v = tid; v < s.nvec; v += kThreads) {
@@ -301,11 +370,14 @@ __device__ __forceinline__ void adam_chunk(const OptimTensor& t, const Span& s, 
     float4 pv = *reinterpret_cast<const float4*>(p + i);
     float4 nv = *reinterpret_cast<const float4*>(nu + i);
     float4 mv = *reinterpret_cast<const float4*>(mu + i);
+    [[maybe_unused]] float4 dv;
+    if constexpr (SLOW) dv = slow_load4<SLOW_VECTOR>(d, i);
     adam_one(gv.x, pv.x, nv.x, mv.x, clipped, gnorm, decay, step, usq, pnsq);
     adam_one(gv.y, pv.y, nv.y, mv.y, clipped, gnorm, decay, step, usq, pnsq);
     adam_one(gv.z, pv.z, nv.z, mv.z, clipped, gnorm, decay, step, usq, pnsq);
     adam_one(gv.w, pv.w, nv.w, mv.w, clipped, gnorm, decay, step, usq, pnsq);
     *reinterpret_cast<float4*>(p + i) = pv;
+    if constexpr (SLOW) slow_store4<SLOW_VECTOR>(d, i, pv, dv, mix, omm);
     *reinterpret_cast<float4*>(nu + i) = nv;
     *reinterpret_cast<float4*>(mu + i) = mv;
   }
@@ -313,13 +385,17 @@ __device__ __forceinline__ void adam_chunk(const OptimTensor& t, const Span& s, 
     float pv = p[i], nv = nu[i], mv = mu[i];
     adam_one(grad_at<BF16>(g, i), pv, nv, mv, clipped, gnorm, decay, step, usq, pnsq);
     p[i] = pv, nu[i] = nv, mu[i] = mv;
+    if constexpr (SLOW) d[i] = slow_one(pv, d[i], mix, omm);
   }
 }
 
+template <bool SLOW>                               // as optim_update_kernel's
 __global__ __launch_bounds__(kThreads) void optim_adam_update_kernel(const OptimTensor* __restrict__ table,
                                                                      const OptimChunk* __restrict__ chunks,
                                                                      int32_t n_chunks, float* __restrict__ partials,
-                                                                     const AdamStep step) {
+                                                                     const AdamStep step,
+                                                                     const uint64_t* __restrict__ slow, float mix,
+                                                                     float omm) {
   __shared__ float lds[2][kThreads / kWave];
   const float* gsq_of = partials;
   float* usq_of = partials + 2 * static_cast<int64_t>(n_chunks);
@@ -336,7 +412,18 @@ __global__ __launch_bounds__(kThreads) void optim_adam_update_kernel(const Optim
     const OptimTensor t = tensor_of(table, chunks, chunk, tensor, offset);
     const Span s = span_of(t, offset);
     float usq = 0.f, pnsq = 0.f;
-    if (t.flags & kOptimBf16) adam_chunk<true>(t, s, clipped, gnorm, step, usq, pnsq);
+    uint64_t d = 0;
+    if constexpr (SLOW) d = slow[tensor];
+    if (SLOW && d) {
+      float* to = reinterpret_cast<float*>(d);
+      if (slow_aligned(t, d)) {
+        if (t.flags & kOptimBf16) adam_chunk<true, true, true>(t, s, clipped, gnorm, step, usq, pnsq, to, mix, omm);
+        else adam_chunk<false, true, true>(t, s, clipped, gnorm, step, usq, pnsq, to, mix, omm);
+      } else {
+        if (t.flags & kOptimBf16) adam_chunk<true, true, false>(t, s, clipped, gnorm, step, usq, pnsq, to, mix, omm);
+        else adam_chunk<false, true, false>(t, s, clipped, gnorm, step, usq, pnsq, to, mix, omm);
+      }
+    } else if (t.flags & kOptimBf16) adam_chunk<true>(t, s, clipped, gnorm, step, usq, pnsq);
     else adam_chunk<false>(t, s, clipped, gnorm, step, usq, pnsq);
     block_sum2<kThreads>(usq, pnsq, lds);
     if (threadIdx.x == 0) {
@@ -369,6 +456,54 @@ __global__ __launch_bounds__(kMetricThreads) void optim_metrics_kernel(const flo
   }
 }
 
+// ---- the slow copy on its own (utils.py:117-119): dst = mix * src + omm * dst.
+// A pure stream, 8 bytes read and 4 written per element; a full chunk is 8 vectors
+// per thread, taken two at a time with both pairs of loads ahead of both stores.
+__global__ __launch_bounds__(kThreads) void slow_update_kernel(const SlowTensor* __restrict__ table,
+                                                               const OptimChunk* __restrict__ chunks, int32_t n_chunks,
+                                                               float mix, float omm) {
+  const int tid = threadIdx.x;
+  for (int32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+    int32_t tensor, offset;
+    const SlowTensor t = tensor_of(table, chunks, chunk, tensor, offset);
+    const Span s = span_of(t, offset);
+    float* dst = reinterpret_cast<float*>(t.dst);
+    const float* src = reinterpret_cast<const float*>(t.src);
+    for (int64_t i = static_cast<int64_t>(s.lo) + tid; i < s.first; i += kThreads)
+      dst[i] = slow_one(src[i], dst[i], mix, omm);
+    int32_t v = tid;
+    for (; v + kThreads < s.nvec; v += 2 * kThreads) {              // both of the pair inside the chunk
+      const int32_t i = s.first + 4 * v, j = i + 4 * kThreads;
+      const float4 a = *reinterpret_cast<const float4*>(src + i);
+      const float4 b = *reinterpret_cast<const float4*>(src + j);
+      float4 x = *reinterpret_cast<const float4*>(dst + i);
+      float4 y = *reinterpret_cast<const float4*>(dst + j);
+      x.x = slow_one(a.x, x.x, mix, omm);
+      x.y = slow_one(a.y, x.y, mix, omm);
+      x.z = slow_one(a.z, x.z, mix, omm);
+      x.w = slow_one(a.w, x.w, mix, omm);
+      y.x = slow_one(b.x, y.x, mix, omm);
+      y.y = slow_one(b.y, y.y, mix, omm);
+      y.z = slow_one(b.z, y.z, mix, omm);
+      y.w = slow_one(b.w, y.w, mix, omm);
+      *reinterpret_cast<float4*>(dst + i) = x;
+      *reinterpret_cast<float4*>(dst + j) = y;
+    }
+    if (v < s.nvec) {                                                // the one left over
+      const int32_t i = s.first + 4 * v;
+      const float4 a = *reinterpret_cast<const float4*>(src + i);
+      float4 x = *reinterpret_cast<const float4*>(dst + i);
+      x.x = slow_one(a.x, x.x, mix, omm);
+      x.y = slow_one(a.y, x.y, mix, omm);
+      x.z = slow_one(a.z, x.z, mix, omm);
+      x.w = slow_one(a.w, x.w, mix, omm);
+      *reinterpret_cast<float4*>(dst + i) = x;
+    }
+    for (int64_t i = static_cast<int64_t>(s.tail) + tid; i < s.hi; i += kThreads)
+      dst[i] = slow_one(src[i], dst[i], mix, omm);
+  }
+}
+
 LaunchCount g_count;
 
 int chunk_blocks(int64_t n_chunks) { return static_cast<int>(n_chunks < kMaxBlocks ? n_chunks : kMaxBlocks); }
@@ -396,16 +531,43 @@ hipError_t launch_optim_grad_norms(const OptimTensor* table, const OptimChunk* c
 hipError_t launch_optim_adam_update(const OptimTensor* table, const OptimChunk* chunks, int64_t n_chunks,
                                     float* partials, const AdamStep& step, hipStream_t stream) {
   if (n_chunks < 1 || n_chunks > INT32_MAX || !table || !chunks || !partials) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(optim_adam_update_kernel, dim3(chunk_blocks(n_chunks)), dim3(kThreads), 0, stream, table, chunks,
-                     static_cast<int32_t>(n_chunks), partials, step);
+  hipLaunchKernelGGL(optim_adam_update_kernel<false>, dim3(chunk_blocks(n_chunks)), dim3(kThreads), 0, stream, table,
+                     chunks, static_cast<int32_t>(n_chunks), partials, step, static_cast<const uint64_t*>(nullptr), 0.f,
+                     0.f);
+  return g_count.launched();
+}
+
+hipError_t launch_optim_adam_update_slow(const OptimTensor* table, const OptimChunk* chunks, int64_t n_chunks,
+                                         float* partials, const AdamStep& step, const uint64_t* slow, float mix,
+                                         float omm, hipStream_t stream) {
+  if (n_chunks < 1 || n_chunks > INT32_MAX || !table || !chunks || !partials || !slow) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(optim_adam_update_kernel<true>, dim3(chunk_blocks(n_chunks)), dim3(kThreads), 0, stream, table,
+                     chunks, static_cast<int32_t>(n_chunks), partials, step, slow, mix, omm);
   return g_count.launched();
 }
 
 hipError_t launch_optim_update(const OptimTensor* table, const OptimChunk* chunks, int64_t n_chunks, float* partials,
                                const OptimStep& step, hipStream_t stream) {
   if (n_chunks < 1 || n_chunks > INT32_MAX || !table || !chunks || !partials) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(optim_update_kernel, dim3(chunk_blocks(n_chunks)), dim3(kThreads), 0, stream, table, chunks,
-                     static_cast<int32_t>(n_chunks), partials, step);
+  hipLaunchKernelGGL(optim_update_kernel<false>, dim3(chunk_blocks(n_chunks)), dim3(kThreads), 0, stream, table, chunks,
+                     static_cast<int32_t>(n_chunks), partials, step, static_cast<const uint64_t*>(nullptr), 0.f, 0.f);
+  return g_count.launched();
+}
+
+hipError_t launch_optim_update_slow(const OptimTensor* table, const OptimChunk* chunks, int64_t n_chunks,
+                                    float* partials, const OptimStep& step, const uint64_t* slow, float mix, float omm,
+                                    hipStream_t stream) {
+  if (n_chunks < 1 || n_chunks > INT32_MAX || !table || !chunks || !partials || !slow) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(optim_update_kernel<true>, dim3(chunk_blocks(n_chunks)), dim3(kThreads), 0, stream, table, chunks,
+                     static_cast<int32_t>(n_chunks), partials, step, slow, mix, omm);
+  return g_count.launched();
+}
+
+hipError_t launch_slow_update(const SlowTensor* table, const OptimChunk* chunks, int64_t n_chunks, float mix, float omm,
+                              hipStream_t stream) {
+  if (n_chunks < 1 || n_chunks > INT32_MAX || !table || !chunks) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(slow_update_kernel, dim3(chunk_blocks(n_chunks)), dim3(kThreads), 0, stream, table, chunks,
+                     static_cast<int32_t>(n_chunks), mix, omm);
   return g_count.launched();
 }
 

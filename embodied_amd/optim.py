@@ -44,6 +44,10 @@ tensor and NaN for the infinite ones.  gnorm == 0 leaves the gradients alone.
 Two paths each, as the heads in `outs.py`: the composed one restates the
 reference line by line in torch ops and is the definition; the fused one is
 csrc/optim.hip.
+
+`SlowModel`: the reference's slow (EMA) target network, embodied/jax/utils.py:94-127,
+`self.slowval.update()` of dreamerv3/agent.py:142: in one launch of its own, or
+inside the update launch of an optimizer it is attached to.
 """
 import ctypes as C
 
@@ -71,7 +75,10 @@ _GRADS = {torch.float32: 0, torch.bfloat16: BF16}
 
 def optimizer_launches():
   """Kernel launches `emb_optim_norms`, `emb_optim_update`, `emb_optim_grad_norms`,
-  `emb_optim_adam_update` and `emb_optim_metrics` have issued in this process."""
+  `emb_optim_adam_update` and `emb_optim_metrics` have issued in this process, and
+  those of `SlowModel`: `emb_slow_update`, one per stand-alone `update()` that is
+  due, and `emb_optim_update_slow` / `emb_optim_adam_update_slow`, which take the
+  place of an attached optimizer's update launch."""
   return _lib.launches('optim')
 
 
@@ -149,6 +156,35 @@ def _path(fused, params, who='LaProp'):
   return bool(fused)
 
 
+def _new_plan(device, counts, record_bytes):
+  """Pinned staging and device buffers for a table of `record_bytes` per tensor
+  and the chunk map of csrc/optim.h over tensors of `counts` elements."""
+  counts = np.array(counts, np.int64)
+  n_chunks = int(sum(-(-int(n) // CHUNK) for n in counts))
+  chunks = torch.empty(max(n_chunks, 1) * 8, dtype=torch.uint8).pin_memory()
+  table = torch.empty(max(len(counts), 1) * record_bytes, dtype=torch.uint8).pin_memory()
+  return {'device': device, 'counts': counts, 'n_chunks': n_chunks, 'host_table': table, 'host_chunks': chunks,
+          'table': torch.empty(table.numel(), dtype=torch.uint8, device=device),
+          'chunks': torch.empty(chunks.numel(), dtype=torch.uint8, device=device), 'addrs': None}
+
+
+def _upload(plan, first, build):
+  """Write the table into pinned memory with `build(table, chunks or None,
+  chunk_capacity, n_chunks out)` and copy it to the device on the stream; the
+  chunk map only the `first` time, it depends on the sizes alone."""
+  if not first:
+    # the pinned staging buffer of the previous upload may still be in flight: a
+    # new one (the host allocator keeps the old block until its copy is done)
+    plan['host_table'] = torch.empty_like(plan['host_table']).pin_memory()
+  counted = C.c_int64(-1)
+  build(plan['host_table'].data_ptr(), plan['host_chunks'].data_ptr() if first else None, plan['n_chunks'],
+        C.byref(counted))
+  assert counted.value == plan['n_chunks'], (counted.value, plan['n_chunks'])
+  plan['table'].copy_(plan['host_table'], non_blocking=True)
+  if first:
+    plan['chunks'].copy_(plan['host_chunks'], non_blocking=True)
+
+
 def _moment_like(param):
   """Zeros of the parameter's shape that start at the parameter's address modulo
   16 bytes: a parameter that is a view at an odd element offset into a flat buffer
@@ -189,6 +225,7 @@ class _TableOptimizer(torch.optim.Optimizer):
     self._sums = None               # the composed path's sums of squares of the last step
     self.table_uploads = 0          # how often the device table was (re)written
     self._stepped = False
+    self._slow = None               # the attached SlowModel
 
   # ------------------------------------------------------------------ both paths
 
@@ -237,6 +274,8 @@ class _TableOptimizer(torch.optim.Optimizer):
       self._composed_step(group, grads, moments, lr, c1, c2)
     group['updates'] += 1
     self._stepped = True
+    if self._slow is not None:
+      self._slow.count += 1         # the update launch wrote the slow copy where it was due
     return loss
 
   def metrics(self):
@@ -279,40 +318,29 @@ class _TableOptimizer(torch.optim.Optimizer):
 
   def _make_plan(self, params, flags):
     device = params[0].device if params else torch.device('cuda')
-    counts = np.array([param.numel() for param in params], np.int64)
-    n_chunks = int(sum(-(-int(n) // CHUNK) for n in counts))
-    chunks = torch.empty(max(n_chunks, 1) * 8, dtype=torch.uint8).pin_memory()
-    table = torch.empty(max(len(params), 1) * RECORD_BYTES, dtype=torch.uint8).pin_memory()
-    plan = {'device': device, 'counts': counts, 'n_chunks': n_chunks, 'host_table': table,
-            'table': torch.empty(table.numel(), dtype=torch.uint8, device=device),
-            'chunks': torch.empty(chunks.numel(), dtype=torch.uint8, device=device),
-            'partials': torch.zeros((4, max(n_chunks, 1)), dtype=torch.float32, device=device),
-            'addrs': None, 'flags': None, 'host_chunks': chunks}
+    plan = _new_plan(device, [param.numel() for param in params], RECORD_BYTES)
+    plan.update(partials=torch.zeros((4, max(plan['n_chunks'], 1)), dtype=torch.float32, device=device), flags=None,
+                slow_addrs=None, slow=None)
     return plan
 
-  def _refresh(self, params, addrs, flags):
+  def _refresh(self, params, addrs, flags, slow_addrs=None):
     """(Re)write the device table on the stream: the first step, and whenever an
     address or a gradient's dtype has changed (gradients come back elsewhere after
-    zero_grad(set_to_none=True), moments after load_state_dict)."""
+    zero_grad(set_to_none=True), moments after load_state_dict); with an attached
+    `SlowModel`, the addresses of its tensors beside it."""
     flag_array = np.array(flags, np.int32)
     plan = self._plan
     first = plan is None
     if first:
       plan = self._plan = self._make_plan(params, flag_array)
-    else:
-      # the pinned staging buffer of the previous upload may still be in flight: a
-      # new one (the host allocator keeps the old block until its copy is done)
-      plan['host_table'] = torch.empty_like(plan['host_table']).pin_memory()
     addr_array = np.array(addrs, np.int64)
-    counted = C.c_int64(-1)
-    api.emb_optim_table(addr_array.ctypes.data, plan['counts'].ctypes.data, flag_array.ctypes.data, len(params),
-                        plan['host_table'].data_ptr(), plan['host_chunks'].data_ptr() if first else None,
-                        plan['n_chunks'], C.byref(counted), None, None)
-    assert counted.value == plan['n_chunks'], (counted.value, plan['n_chunks'])
-    plan['table'].copy_(plan['host_table'], non_blocking=True)
-    if first:
-      plan['chunks'].copy_(plan['host_chunks'], non_blocking=True)
-    plan['addrs'], plan['flags'] = addrs, flags
+    _upload(plan, first, lambda table, chunks, capacity, counted: api.emb_optim_table(
+        addr_array.ctypes.data, plan['counts'].ctypes.data, flag_array.ctypes.data, len(params), table, chunks,
+        capacity, counted, None, None))
+    if slow_addrs is not None:
+      staged = torch.tensor(slow_addrs or [0], dtype=torch.int64).pin_memory()
+      plan['slow'] = staged.to(plan['device'], non_blocking=True)
+    plan['addrs'], plan['flags'], plan['slow_addrs'] = addrs, flags, slow_addrs
     self.table_uploads += 1
 
   def _tables(self, group, grads, moments):
@@ -324,11 +352,20 @@ class _TableOptimizer(torch.optim.Optimizer):
     for param, grad, state, decays in zip(params, grads, moments, self.wd_mask):
       addrs += (param.data_ptr(), grad.data_ptr(), state['nu'].data_ptr(), state['mu'].data_ptr())
       flags.append(_GRADS[grad.dtype] | (DECAY if wd and decays else 0))
+    slow_addrs = None if self._slow is None else self._slow._addresses_for(params)
     plan = self._plan
-    if plan is None or plan['addrs'] != addrs or plan['flags'] != flags:
-      self._refresh(params, addrs, flags)
+    if plan is None or plan['addrs'] != addrs or plan['flags'] != flags or plan['slow_addrs'] != slow_addrs:
+      self._refresh(params, addrs, flags, slow_addrs)
       plan = self._plan
     return plan
+
+  def _slow_args(self, plan):
+    """(slow, mix, omm) of the `_slow` entry points where the attached `SlowModel`
+    is due on this step, else None: the plain entry point."""
+    slow = self._slow
+    if slow is None or slow.count % slow.every:
+      return None
+    return plan['slow'].data_ptr(), slow.mix, slow.omm
 
 
 class LaProp(_TableOptimizer):
@@ -395,8 +432,13 @@ class LaProp(_TableOptimizer):
     table, chunks, partials = plan['table'].data_ptr(), plan['chunks'].data_ptr(), plan['partials'].data_ptr()
     beta1, beta2 = group['beta1'], group['beta2']
     api.emb_optim_norms(table, chunks, plan['n_chunks'], partials, stream)
-    api.emb_optim_update(table, chunks, plan['n_chunks'], partials, lr, beta1, 1 - beta1, c1, beta2, 1 - beta2, c2,
-                         group['eps'], group['agc'], group['pmin'], group['wd'], int(group['nesterov']), stream)
+    args = (table, chunks, plan['n_chunks'], partials, lr, beta1, 1 - beta1, c1, beta2, 1 - beta2, c2, group['eps'],
+            group['agc'], group['pmin'], group['wd'], int(group['nesterov']))
+    slow = self._slow_args(plan)
+    if slow:
+      api.emb_optim_update_slow(*args, *slow, stream)
+    else:
+      api.emb_optim_update(*args, stream)
 
 
 class Adam(_TableOptimizer):
@@ -468,5 +510,224 @@ class Adam(_TableOptimizer):
     table, chunks, partials = plan['table'].data_ptr(), plan['chunks'].data_ptr(), plan['partials'].data_ptr()
     beta1, beta2 = group['beta1'], group['beta2']
     api.emb_optim_grad_norms(table, chunks, plan['n_chunks'], partials, stream)
-    api.emb_optim_adam_update(table, chunks, plan['n_chunks'], partials, lr, beta1, 1 - beta1, c1, beta2, 1 - beta2, c2,
-                              group['eps'], group['clip'], group['wd'], stream)
+    args = (table, chunks, plan['n_chunks'], partials, lr, beta1, 1 - beta1, c1, beta2, 1 - beta2, c2, group['eps'],
+            group['clip'], group['wd'])
+    slow = self._slow_args(plan)
+    if slow:
+      api.emb_optim_adam_update_slow(*args, *slow, stream)
+    else:
+      api.emb_optim_adam_update(*args, stream)
+
+
+# ---------------------------------------------------------------- the slow model
+
+def _slow_geometry():
+  record = C.c_int64(0)
+  api.emb_slow_table(None, None, 0, None, None, 0, None, C.byref(record))
+  return record.value
+
+
+SLOW_RECORD_BYTES = _slow_geometry()                  # csrc/optim.h: SlowTensor
+
+
+def slow_mix(rate):
+  """(mix, omm) as the reference forms them on a float32 scalar (utils.py:117-118):
+  mix = float32(rate) and omm = float32(1) - mix, the subtraction in float32.  A
+  double `1 - rate` rounded once can differ from that in the last bit."""
+  mix = np.float32(rate)
+  return mix, np.float32(1) - mix
+
+
+def _named_tensors(who, thing):
+  """(keys, tensors) of a module's `named_parameters()` or of a sequence of tensors."""
+  if isinstance(thing, torch.nn.Module):
+    named = dict(thing.named_parameters())
+    return list(named), list(named.values())
+  if torch.is_tensor(thing) or isinstance(thing, (str, bytes, dict)):
+    raise TypeError(f'SlowModel: {who} is a {type(thing).__name__}, not a torch.nn.Module or a sequence of tensors')
+  tensors = list(thing)
+  return list(range(len(tensors))), tensors
+
+
+# `SlowModel(fused=None)`: the kernel wherever it fits.  On the MI355X the median of
+# `update()` is below the composed one at all four rows of
+# profiles/slow_model_bench.txt -- the reference's value MLP at size1m 7.9 us
+# against 160.4, at size200m 23.6 / 140.7, at size400m 50.8 / 171.1, 1 M parameters
+# in 40 tensors 13.2 / 607.9 -- so there is no crossover constant here either.
+
+
+class SlowModel:
+  """`SlowModel(model, source, rate=1.0, every=1, fused=None)`: the reference's
+  slowly updated copy of a network (embodied/jax/utils.py:94-127), DreamerV3's
+  `slowval` (dreamerv3/agent.py:142; its `pred()` is the `slow_pred` of
+  `TwoHot.loss_sum`, `dreamer_targets` and `imag_metrics`).
+
+  model, source   two `torch.nn.Module`s whose `named_parameters()` have the same
+                  keys and shapes, or two sequences of tensors of equal length;
+                  CUDA float32 throughout.  Construction copies source into model
+                  (the reference's `_initonce`); that is no update.
+  rate            1, or 0 <= rate < 0.5 (utils.py:97)
+  every           a whole number of updates, 1 or more
+  fused           None: the kernel where it fits; True / False force a path, True
+                  raises where it does not fit and says why
+
+  `update()`, on the calls where `count % every == 0` (count starts at 0), per
+  element and in float32, two rounded products and one rounded sum:
+
+      dst = mix * src + omm * dst       mix = float32(rate), omm = float32(1) - mix
+
+  in ONE launch for all tensors (csrc/optim.hip: slow_update_kernel); the composed
+  path, the definition, is `dst.mul_(omm).add_(src * mix)` per tensor.  Then
+  `count += 1`.  Calls and attribute access go to `model`.
+
+  `attach(optimizer)` folds the update into a fused `LaProp` or `Adam` whose
+  parameters include every source tensor: from then on `optimizer.step()` writes
+  the slow copy from the new parameter it holds in registers, in the update launch
+  it issues anyway, and advances `count`; `update()` raises, `detach()` undoes it.
+
+  Different from the reference, on purpose:
+  * An off-step (`count % every != 0`) touches nothing.  The reference computes
+    `0 * src + 1 * dst`, which turns a non-finite source element into a NaN in the
+    copy.  On an update step the expression is evaluated as written: a NaN or an
+    infinity behaves as in the reference and stays inside its element.
+  * `count` is a Python int on the host.  Under graph capture an `update()` replays
+    the decision taken at capture time: right for `every == 1`, unsupported otherwise.
+  """
+
+  def __init__(self, model, source, rate=1.0, every=1, fused=None):
+    self.model = model
+    self.source = source
+    self._set_schedule(rate, every)
+    keys, dst = _named_tensors('model', model)
+    source_keys, src = _named_tensors('source', source)
+    if set(keys) != set(source_keys) or len(keys) != len(source_keys):
+      raise ValueError(f'SlowModel: model and source differ in their parameters: {sorted(map(str, set(keys) ^ set(source_keys)))[:4]} '
+                       f'({len(keys)} against {len(source_keys)})')
+    order = {key: i for i, key in enumerate(keys)}
+    dst = [dst[order[key]] for key in source_keys]                 # in the source's order
+    for index, (d, s) in enumerate(zip(dst, src)):
+      _check_param(index, s)
+      _check_param(index, d)
+      if d.shape != s.shape:
+        raise ValueError(f'SlowModel: parameter {index} ({source_keys[index]!r}) is {tuple(d.shape)} in model and '
+                         f'{tuple(s.shape)} in source')
+      if d.device != src[0].device or s.device != src[0].device:
+        raise ValueError(f'SlowModel: parameter {index} ({source_keys[index]!r}) is not on {src[0].device}')
+      if d is s or (d.numel() and d.data_ptr() == s.data_ptr()):
+        raise ValueError(f'SlowModel: parameter {index} ({source_keys[index]!r}) of model IS the source\'s tensor')
+    self._dst, self._src = dst, src
+    self.fused = _path(fused, dst + src, 'SlowModel')
+    self.count = 0
+    self.table_uploads = 0            # how often the device table was (re)written
+    self._plan = None
+    self._attached = None
+    with torch.no_grad():             # utils.py:121-124, _initonce
+      for d, s in zip(dst, src):
+        d.copy_(s)
+
+  def _set_schedule(self, rate, every):
+    rate = float(rate)
+    if not (rate == 1.0 or 0.0 <= rate < 0.5):
+      raise ValueError(f'SlowModel: rate = {rate!r} must be 1 or in [0, 0.5)')
+    if isinstance(every, bool) or int(every) != every or every < 1:
+      raise ValueError(f'SlowModel: every = {every!r} must be a whole number of updates, 1 or more')
+    self.rate, self.every = rate, int(every)
+    mix, omm = slow_mix(rate)
+    self.mix, self.omm = float(mix), float(omm)       # float32 values, exact as Python floats
+
+  def __getattr__(self, name):                        # only what the instance itself does not have
+    if name.startswith('__') or name in ('model', 'source'):
+      raise AttributeError(name)
+    return getattr(self.model, name)
+
+  def __call__(self, *args, **kwargs):
+    return self.model(*args, **kwargs)
+
+  # ------------------------------------------------------------------- stand-alone
+
+  @torch.no_grad()
+  def update(self):
+    if self._attached is not None:
+      raise RuntimeError('SlowModel.update: attached to an optimizer, whose step() has done it (detach() first)')
+    if self.count % self.every == 0:
+      if self.fused:
+        self._fused_update()
+      else:
+        for d, s in zip(self._dst, self._src):        # utils.py:118, the definition
+          d.mul_(self.omm).add_(s * self.mix)
+    self.count += 1
+
+  def _fused_update(self):
+    addrs = []
+    for index, (d, s) in enumerate(zip(self._dst, self._src)):
+      if not (d.is_contiguous() and s.is_contiguous()):
+        raise ValueError(f'SlowModel.update (fused): parameter {index} is not contiguous')
+      addrs += (d.data_ptr(), s.data_ptr())
+    plan = self._plan
+    if plan is None or plan['addrs'] != addrs:
+      first = plan is None
+      if first:
+        device = self._src[0].device if self._src else torch.device('cuda')
+        plan = self._plan = _new_plan(device, [s.numel() for s in self._src], SLOW_RECORD_BYTES)
+      addr_array = np.array(addrs, np.int64)
+      _upload(plan, first, lambda table, chunks, capacity, counted: api.emb_slow_table(
+          addr_array.ctypes.data, plan['counts'].ctypes.data, len(self._src), table, chunks, capacity, counted, None))
+      plan['addrs'] = addrs
+      self.table_uploads += 1
+    if plan['n_chunks']:
+      api.emb_slow_update(plan['table'].data_ptr(), plan['chunks'].data_ptr(), plan['n_chunks'], self.mix, self.omm,
+                          _lib.raw_stream(plan['device']))
+
+  # ------------------------------------------------------- inside an optimizer's step
+
+  def attach(self, optimizer):
+    """Have `optimizer.step()` write the slow copy in its update launch."""
+    if self._attached is not None:
+      raise RuntimeError('SlowModel.attach: already attached (detach() first)')
+    if not isinstance(optimizer, _TableOptimizer) or not optimizer.fused:
+      raise TypeError('SlowModel.attach: a fused embodied_amd.optim.LaProp or Adam, the composed path has no launch '
+                      'to fold the update into')
+    if optimizer._slow is not None:
+      raise RuntimeError('SlowModel.attach: the optimizer already has a SlowModel, one per optimizer')
+    params = optimizer.param_groups[0]['params']
+    where = {id(param): i for i, param in enumerate(params)}
+    taken = {param.data_ptr() for param in params if param.numel()}
+    slots = []
+    for index, (d, s) in enumerate(zip(self._dst, self._src)):
+      if id(s) not in where:
+        raise ValueError(f'SlowModel.attach: source tensor {index} of shape {tuple(s.shape)} is not a parameter of the '
+                         'optimizer')
+      if d.numel() and d.data_ptr() in taken:
+        raise ValueError(f'SlowModel.attach: model tensor {index} is a parameter of the optimizer')
+      if d.device != params[0].device:
+        raise ValueError(f'SlowModel.attach: model tensor {index} is not on the optimizer\'s device')
+      slots.append(where[id(s)])
+    self._slots = slots
+    self._attached = optimizer
+    optimizer._slow = self
+
+  def detach(self):
+    if self._attached is None:
+      raise RuntimeError('SlowModel.detach: not attached')
+    self._attached._slow = None
+    self._attached = None
+
+  def _addresses_for(self, params):
+    """One address per parameter of the optimizer: its slow copy, 0 for none."""
+    out = [0] * len(params)
+    for index, (slot, d, s) in enumerate(zip(self._slots, self._dst, self._src)):
+      if params[slot] is not s:
+        raise ValueError(f'SlowModel: source tensor {index} is no longer parameter {slot} of the optimizer')
+      if not d.is_contiguous():
+        raise ValueError(f'SlowModel (attached): model tensor {index} is not contiguous')
+      out[slot] = d.data_ptr() if d.numel() else 0
+    return out
+
+  # --------------------------------------------------------------------------- state
+
+  def state_dict(self):
+    return {'count': self.count, 'rate': self.rate, 'every': self.every}
+
+  def load_state_dict(self, state):
+    self._set_schedule(state['rate'], state['every'])
+    self.count = int(state['count'])

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports (158 functions). */
+ * it exports (162 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -53,7 +53,8 @@ extern "C" {
  * emb_recon_loss_launches, emb_normal_policy_loss, emb_normal_policy_loss_grad,
  * emb_normal_sample, emb_philox_normal, emb_normal_policy_launches,
  * emb_block_linear_plan, emb_stat_rows, emb_stat_rows_launches, emb_mean_fill,
- * emb_optim_grad_norms, emb_optim_adam_update
+ * emb_optim_grad_norms, emb_optim_adam_update, emb_slow_table, emb_slow_update,
+ * emb_optim_update_slow, emb_optim_adam_update_slow
  * (additions only).                                                          */
 #define EMB_ABI_VERSION 5
 
@@ -863,8 +864,49 @@ int32_t emb_optim_grad_norms(const void* table, const void* chunks, int64_t n_ch
 int32_t emb_optim_adam_update(const void* table, const void* chunks, int64_t n_chunks, void* partials, float lr,
                               float beta1, float omb1, float c1, float beta2, float omb2, float c2, float eps,
                               float clip, float wd, void* stream);
-/* Kernel launches the five launching entry points above have issued in this
- * process, counted where the kernels are launched.                             */
+/* The slow (EMA) copy of a set of float32 tensors, the reference's SlowModel
+ * (embodied/jax/utils.py:94-127; dreamerv3/agent.py:142 `self.slowval.update()`),
+ * per element, float32, two rounded products and one rounded sum:
+ *   dst = mix * src + omm * dst                                 (utils.py:118)
+ * The caller hands over mix = the rate as float32 and omm = 1 - mix FORMED IN
+ * float32, as the reference forms it on a float32 scalar, and decides on the host
+ * whether this is an update step (utils.py:117, count % every == 0): on any other
+ * step it calls nothing.  A NaN or an infinity in src or dst stays in its element.
+ *   emb_slow_table   host only, no HIP call; as emb_optim_table: one record of
+ *                    `record_bytes` per tensor from addrs (tensors, 2) = the device
+ *                    addresses of dst and src and counts (tensors), one 8-byte
+ *                    record per chunk into `chunks`.  A tensor whose src is 16-byte
+ *                    aligned where dst is takes 16-byte accesses with scalar
+ *                    ragged ends, any other goes scalar.  dst == src is refused.
+ *   emb_slow_update  one launch over such a table: reads 8 and writes 4 bytes per
+ *                    element.  n_chunks = 0 launches nothing.
+ *   emb_optim_update_slow, emb_optim_adam_update_slow
+ *                    emb_optim_update / emb_optim_adam_update with the slow copy
+ *                    written in the same launch from the p_new it holds in
+ *                    registers: `slow` is (tensors,) uint64 on device, the address
+ *                    of each table entry's slow copy or 0 for none (the tensor is
+ *                    then updated as by the plain entry point); d = mix * p_new +
+ *                    omm * d at the same element index.  p, nu, mu and the
+ *                    partials receive the same bits as from the plain entry point.
+ *                    The caller guarantees that a slow copy is float32 of its
+ *                    tensor's size, 4-byte aligned, and overlaps nothing else in
+ *                    the table.
+ * EMB_ERR_INVALID before any launch: what emb_optim_table, emb_optim_update and
+ * emb_optim_adam_update refuse, a NULL `slow`, mix outside [0, 1], omm not finite
+ * or outside [0, 1].                                                           */
+int32_t emb_slow_table(const int64_t* addrs, const int64_t* counts, int64_t tensors, void* table, void* chunks,
+                       int64_t chunk_capacity, int64_t* n_chunks, int64_t* record_bytes);
+int32_t emb_slow_update(const void* table, const void* chunks, int64_t n_chunks, float mix, float omm, void* stream);
+int32_t emb_optim_update_slow(const void* table, const void* chunks, int64_t n_chunks, void* partials, float lr,
+                              float beta1, float omb1, float c1, float beta2, float omb2, float c2, float eps, float agc,
+                              float pmin, float wd, int32_t nesterov, const void* slow, float mix, float omm,
+                              void* stream);
+int32_t emb_optim_adam_update_slow(const void* table, const void* chunks, int64_t n_chunks, void* partials, float lr,
+                                   float beta1, float omb1, float c1, float beta2, float omb2, float c2, float eps,
+                                   float clip, float wd, const void* slow, float mix, float omm, void* stream);
+/* Kernel launches the eight launching entry points above (emb_optim_norms to
+ * emb_optim_adam_update_slow; the two table builders launch nothing) have issued
+ * in this process, counted where the kernels are launched.                     */
 int32_t emb_optim_launches(int64_t* count);
 
 /* ---- Norm followed by the activation, float32 arithmetic on device
