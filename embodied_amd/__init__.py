@@ -41,6 +41,7 @@ from .outs import MSE, ImageMSE, Binary, recon_loss_launches
 from .outs import Normal, normal_policy_loss, philox_normal, normal_policy_launches
 from . import nets
 from .nets import NormAct, norm_act, gru_gate, norm_act_launches, gru_gate_launches
+from .nets import PoolNormAct, NormActUpsample, pool_norm_act, norm_act_upsample, conv_stage_launches
 from . import optim
 from .optim import LaProp, Adam, SlowModel, optimizer_launches
 from .utils import Counter, LocalClock

@@ -263,6 +263,11 @@ SIGNATURES = {
     'emb_norm_act': [p, p, p, i32, i64, i64, i32, i32, f32, p, p],
     'emb_norm_act_grad': [p, p, p, p, i32, i64, i64, i32, i32, f32, p, p, p, p, i64, p],
     'emb_norm_act_launches': [p],
+    'emb_pool_norm_act': [p, p, p, i32, i64, i64, i64, i64, i32, i32, f32, p, p],
+    'emb_pool_norm_act_grad': [p, p, p, p, i32, i64, i64, i64, i64, i32, i32, f32, p, p, p, p, i64, p],
+    'emb_norm_act_upsample': [p, p, p, i32, i64, i64, i64, i64, i32, i32, f32, p, p],
+    'emb_norm_act_upsample_grad': [p, p, p, p, i32, i64, i64, i64, i64, i32, i32, f32, p, p, p, p, i64, p],
+    'emb_conv_stage_launches': [p],
     'emb_gru_gate': [p, p, i32, i64, i64, i64, p, p],
     'emb_gru_gate_grad': [p, p, p, i32, i64, i64, i64, p, p, p],
     'emb_gru_gate_launches': [p],

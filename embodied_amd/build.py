@@ -21,6 +21,7 @@ OBJ = HERE / 'build'
 SOURCES = ['movers.hip', 'step.hip', 'scans.hip', 'synth_env.hip', 'direct_comm.hip', 'normalize.hip', 'ppo_targets.hip',
            'dreamer_targets.hip', 'twohot.hip', 'onehot_kl.hip', 'policy_loss.hip', 'optim.hip',
            'norm_act.hip', 'gru_gate.hip', 'onehot_sample.hip', 'norm_act_abi.cpp', 'gru_gate_abi.cpp',
+           'conv_stage.hip', 'conv_stage_abi.cpp',
            'onehot_sample_abi.cpp', 'recon_loss.hip', 'recon_loss_abi.cpp', 'normal_policy.hip',
            'normal_policy_abi.cpp', 'block_linear_abi.cpp', 'stat_rows.hip', 'stat_rows_abi.cpp',
            'replay_abi.cpp', 'index_abi.cpp', 'kernels_abi.cpp', 'env_abi.cpp', 'comm_abi.cpp', 'normalize_abi.cpp',
@@ -123,7 +124,14 @@ def build(force=False, verbose=True):
         raise RuntimeError('kernels that use scratch memory:\n' + listing)
       print('warning: kernels that use scratch memory:\n' + listing, file=sys.stderr)
     import re
-    rest = [l for l in res.stderr.splitlines() if 'kernel-resource-usage' not in l
+    said = res.stderr.splitlines()
+    # (a remark about a kernel that lives in a header comes behind its include
+    # trail: that trail goes with the remark, a warning's or an error's stays)
+    for i in range(len(said) - 1, -1, -1):
+      if said[i].startswith('In file included from') and i + 1 < len(said) and (
+          'kernel-resource-usage' in said[i + 1] or said[i + 1] == ''):
+        said[i] = ''
+    rest = [l for l in said if 'kernel-resource-usage' not in l
             and not re.match(r'^\s*(\d+\s*)?\|', l) and not l.lstrip().startswith('^')
             and 'remarks generated' not in l]
     if verbose and any(l.strip() for l in rest):

@@ -48,7 +48,7 @@ class SyntheticBatchEnv:
     # ring > 0: observations are written into `ring` rotating sets of output
     # buffers instead of fresh tensors (like vector envs that own their output
     # arrays): a returned dict is overwritten `ring` steps later.
-    self.ring = [self._alloc() for _ in range(ring)]
+    self.ring = [self._alloc_slot() for _ in range(ring)]
     # (the ring's tensors never change: their addresses are taken once)
     self._ring_ptrs = [tuple(v.data_ptr() for v in obs.values()) for obs in self.ring]
     self._counters_ptr = self.counters.data_ptr()
@@ -85,6 +85,26 @@ class SyntheticBatchEnv:
         'is_first': _lib.empty((n,), torch.bool, dev),
         'is_last': _lib.empty((n,), torch.bool, dev),
         'is_terminal': _lib.empty((n,), torch.bool, dev),
+    }
+
+  def _alloc_slot(self):
+    """A ring slot's output set: as `_alloc`, but `reward` and the three flag
+    buffers are views of ONE allocation, each at a multiple of 256 bytes.  The
+    fused step launch addresses the flags as 32-bit offsets from `reward`
+    (csrc/synth_fused.h `offsets`); four tensors of their own lie wherever the
+    caching allocator has a free block, which in a long-lived process can be
+    more than 2 GiB apart -- the launch is then refused for that slot for good."""
+    n, dev = self.n, self.device
+    pitch = lambda size: -(-size // 256) * 256
+    at_flags = pitch(4 * n)
+    slab = _lib.empty((at_flags + 3 * pitch(n),), torch.uint8, dev)
+    flag = lambda k: slab[at_flags + k * pitch(n): at_flags + k * pitch(n) + n].view(torch.bool)
+    return {
+        'image': _lib.empty((n, *self.shape), torch.uint8, dev),
+        'reward': slab[:4 * n].view(torch.float32),
+        'is_first': flag(0),
+        'is_last': flag(1),
+        'is_terminal': flag(2),
     }
 
   def step(self, acts, unmasked=None):

@@ -33,6 +33,21 @@ GRU_GATE_MAX_ELEMENTS = 2 ** 31 - 1                # of x: rows * 3 * deter
 # gradient launch has at most this many workgroups, each leaves one row of partial sums
 _WAVE_UNITS, _MAX_PARTIALS = 1024, 512
 
+# The conv-stage kernels (csrc/conv_stage.h): a pixel of at most 1024 channels in
+# the registers of one wave64, 32-bit indices into the larger tensor; the gradient
+# launch has at most _STAGE_MAX_PARTIALS workgroups, one row of partial sums each.
+# Structural, not a crossover: the fused median is below both rivals -- the
+# composed path and amax + norm_act(fused=True) / norm_act(fused=True) +
+# repeat_interleave -- at all 72 rows of profiles/conv_stage_bench.txt.  Pool
+# (1024, 64, 64, 128) f32: forward 491.2 us against 1630.8 and 986.2, forward +
+# backward 1456.6 against 10676.2 and 7977.0; (16, 64, 64, 128) f32: 16.9 / 59.8 /
+# 24.7 and 115.5 / 250.8 / 158.8; upsample (1024, 32, 32, 128) bf16: 259.5 / 2264.2 /
+# 1598.9 and 684.8 / 5960.5 / 3793.6 -- so no size constant sits beside
+# `_pool_path` or `_upsample_path`.
+CONV_STAGE_MAX_UNITS = 1024
+CONV_STAGE_MAX_ELEMENTS = 2 ** 31 - 1
+_STAGE_MAX_PARTIALS = 1024
+
 IMPLS = {'rms': 0, 'layer': 1}
 ACTS = {'none': 0, 'silu': 1, 'gelu': 2, 'relu': 3}
 _DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
@@ -41,6 +56,11 @@ _DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
 def norm_act_launches():
   """Kernel launches `emb_norm_act` and `emb_norm_act_grad` have issued in this process."""
   return _lib.launches('norm_act')
+
+
+def conv_stage_launches():
+  """Kernel launches `emb_pool_norm_act*` and `emb_norm_act_upsample*` have issued in this process."""
+  return _lib.launches('conv_stage')
 
 
 def gru_gate_launches():
@@ -262,6 +282,204 @@ class NormAct(torch.nn.Module):
 
   def extra_repr(self):
     return f'{self.units}, impl={self.impl!r}, act={self.act!r}, eps={self.eps:g}'
+
+
+def _stage_lanes(units):
+  """Lanes of a wave64 that share one pixel (conv_stage_lanes in csrc/conv_stage.h)."""
+  return 8 if units <= 64 else 16 if units <= 128 else 32 if units <= 256 else 64
+
+
+def _stage_partial_floats(pixels, units):
+  """float32 values `emb_pool_norm_act_grad` / `emb_norm_act_upsample_grad` want for
+  their partial sums over `pixels` Norm rows (conv_stage_partials in
+  csrc/conv_stage.h; tests/test_conv_stage_host.py holds the two against each other)."""
+  per_block = 4 * (64 // _stage_lanes(units))
+  return 2 * min(-(-pixels // per_block), _STAGE_MAX_PARTIALS) * units
+
+
+def _stage_path(who, fused, units, elements):
+  row, index = 1 <= units <= CONV_STAGE_MAX_UNITS, elements <= CONV_STAGE_MAX_ELEMENTS
+  if row and index:
+    return fused is None or bool(fused)
+  return _fused_path(
+      who, fused,
+      (row, f'{units} channels, the kernels keep a pixel of at most {CONV_STAGE_MAX_UNITS} in one wave\'s registers'),
+      (index, f'{elements} elements in the larger tensor, the kernels index at most 2^31 - 1'))
+
+
+def _pool_path(fused, images, height, width, units):
+  """True: the kernels, False: the composed path (`pool_norm_act` says when).  As
+  `_norm_path`: below the composed path and below `amax` + the fused `norm_act`
+  at all 40 pool rows of profiles/conv_stage_bench.txt, so wherever they fit."""
+  return _stage_path('pool_norm_act', fused, units, images * height * width * units)
+
+
+def _upsample_path(fused, images, height, width, units):
+  """True: the kernels, False: the composed path (`norm_act_upsample` says when).
+  Below both rivals at all 32 upsample rows of profiles/conv_stage_bench.txt."""
+  return _stage_path('norm_act_upsample', fused, units, images * 4 * height * width * units)
+
+
+def _composed_pool_norm_act(x, scale, shift, impl, act, eps):
+  """rssm.py:239-241 operation by operation: the 2x2 windows as two axes of a
+  reshape, their max (torch.amax: a NaN wins, tied maxima share the gradient
+  equally), then `_composed_norm_act`."""
+  *lead, height, width, units = x.shape
+  pooled = x.reshape(*lead, height // 2, 2, width // 2, 2, units).amax((-4, -2))
+  return _composed_norm_act(pooled, scale, shift, impl, act, eps)
+
+
+def _composed_norm_act_upsample(x, scale, shift, impl, act, eps):
+  """rssm.py:327, 336: `_composed_norm_act`, then every pixel repeated 2x2.  jnp's
+  `x.repeat(2, axis)` repeats element by element: torch's `repeat_interleave`
+  (`Tensor.repeat` tiles the whole axis instead)."""
+  return _composed_norm_act(x, scale, shift, impl, act, eps).repeat_interleave(2, -2).repeat_interleave(2, -3)
+
+
+class _FusedStage(torch.autograd.Function):
+  """A conv stage's tail on the kernels (`pool`: 2x2 max + Norm + act, else Norm +
+  act + 2x2 repeat): one launch forward; backward one launch, two with a gradient
+  for `scale` or `shift`."""
+
+  @staticmethod
+  def forward(ctx, x, scale, shift, impl, act, eps, pool):
+    height, width, units = x.shape[-3:]
+    flat = x.detach().reshape(-1, height, width, units).contiguous()
+    images = flat.shape[0]
+    result = (images, height // 2, width // 2, units) if pool else (images, 2 * height, 2 * width, units)
+    out = torch.empty(result, dtype=flat.dtype, device=flat.device)
+    scale = None if scale is None else scale.detach().contiguous()
+    shift = None if shift is None else shift.detach().contiguous()
+    entry = api.emb_pool_norm_act if pool else api.emb_norm_act_upsample
+    entry(flat.data_ptr(), _address(scale), _address(shift), _DTYPES[x.dtype], images, height, width, units, impl, act,
+          eps, out.data_ptr(), _lib.raw_stream(x.device))
+    ctx.saved = (flat, scale, shift, impl, act, eps, pool, x.shape, out.shape)
+    ctx.set_materialize_grads(False)
+    return out.view(*x.shape[:-3], *result[1:])
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    if gout is None:
+      return (None,) * 7
+    flat, scale, shift, impl, act, eps, pool, shape, out_shape = ctx.saved
+    images, height, width, units = flat.shape
+    want_x, want_scale, want_shift = ctx.needs_input_grad[:3]
+    want_shift = want_shift and impl == IMPLS['layer']
+    gout = gout.to(flat.dtype).reshape(out_shape).contiguous()
+    dx = torch.empty_like(flat) if want_x else None
+    dscale = _lib.empty((units,), torch.float32, flat.device) if want_scale else None
+    dshift = _lib.empty((units,), torch.float32, flat.device) if want_shift else None
+    partials, floats = None, 0
+    if want_scale or want_shift:
+      pixels = images * (height // 2) * (width // 2) if pool else images * height * width
+      floats = _stage_partial_floats(pixels, units)
+      partials = _lib.empty((floats,), torch.float32, flat.device)
+    if dx is None and dscale is None and dshift is None:
+      return (None,) * 7
+    entry = api.emb_pool_norm_act_grad if pool else api.emb_norm_act_upsample_grad
+    entry(flat.data_ptr(), _address(scale), _address(shift), gout.data_ptr(), _DTYPES[flat.dtype], images, height, width,
+          units, impl, act, eps, _address(dx), _address(dscale), _address(dshift), _address(partials), floats,
+          _lib.raw_stream(flat.device))
+    if ctx.needs_input_grad[2] and dshift is None:      # rms does not read its shift
+      dshift = torch.zeros_like(shift)
+    return (None if dx is None else dx.view(shape), dscale, dshift, None, None, None, None)
+
+
+def _stage(who, pool, x, scale, shift, impl, act, eps, fused):
+  """The checks of `norm_act` for an `x` of (..., H, W, C), then the path."""
+  _check_device(who, x)
+  if x.dtype not in _DTYPES:
+    raise TypeError(f'{who}: x must be float32 or bfloat16, got {x.dtype}')
+  impl, eps = _eps_of(impl, eps)
+  if impl not in IMPLS:
+    raise ValueError(f'{who}: impl = {impl!r}, needs one of {sorted(IMPLS)}')
+  if act not in ACTS:
+    raise ValueError(f'{who}: act = {act!r}, needs one of {sorted(ACTS)}')
+  eps = float(eps)
+  if not (np.isfinite(eps) and eps >= 0):
+    raise ValueError(f'{who}: eps = {eps}, needs a finite value that is not negative')
+  if x.dim() < 3 or min(x.shape[-3:]) < 1:
+    raise ValueError(f'{who}: x of shape {tuple(x.shape)}, needs (..., H, W, C), channels last')
+  height, width, units = x.shape[-3:]
+  if pool and (height % 2 or width % 2):
+    raise ValueError(f'{who}: x of shape {tuple(x.shape)}, the 2x2 windows need an even H and W (rssm.py:239)')
+  scale = _check_param(who, 'scale', scale, units, x)
+  shift = _check_param(who, 'shift', shift, units, x)
+  if impl == 'rms' and shift is not None:
+    raise ValueError(f'{who}: rms takes no shift (nets.py:382-386)')
+  images = int(np.prod(x.shape[:-3], dtype=np.int64))
+  path = _pool_path if pool else _upsample_path
+  if path(fused, images, height, width, units) and images > 0:
+    return _FusedStage.apply(x, scale, shift, IMPLS[impl], ACTS[act], eps, pool)
+  composed = _composed_pool_norm_act if pool else _composed_norm_act_upsample
+  return composed(x, scale, shift, impl, act, eps)
+
+
+def pool_norm_act(x, scale=None, shift=None, impl='rms', act='silu', eps=1e-4, fused=None):
+  """The tail of an `Encoder` stage with `strided=False` (dreamerv3/rssm.py:238-241):
+  after the stage's `Conv2D`, the max over 2x2 windows, `Norm` and `act`.  `x` is
+  a CUDA tensor (..., H, W, C), channels last as in the reference, float32 or
+  bfloat16, H and W even (the reference's reshape takes no others); the result
+  is (..., H/2, W/2, C) in the dtype of `x`, differentiable once with respect to
+  `x`, `scale` and `shift`.  `scale`, `shift`, `impl`, `act` and `eps` as `norm_act`.
+  A non-contiguous `x` (a channels-first conv output, permuted) is copied.
+
+  Two paths, as `norm_act`.  Composed is the definition at every size:
+  `x.reshape(..., H/2, 2, W/2, 2, C).amax((-4, -2))`, then `norm_act`'s composed
+  path.  Fused is `emb_pool_norm_act` / `emb_pool_norm_act_grad`, 1 .. 1024
+  channels and at most 2^31 - 1 elements of `x`: ONE launch forward that reads the
+  four window rows, keeps the pooled row in registers and writes the activated
+  row; backward ONE launch that recomputes the pooled row from `x` (nothing is
+  saved but `x`) and writes all of `dx`, two with a gradient for `scale` or
+  `shift`; no atomics, the same bits run to run.  `fused=None`, True, False and
+  zero images as `norm_act`.
+
+  Ties: among the positions of a window that equal its max the gradient is
+  split equally (torch.amax; jax's reduce_max rule does the same), the others
+  get exactly 0.  Selecting a max is exact, so the pool adds no rounding and the
+  documented difference is `norm_act`'s alone.
+
+  Non-finite inputs.  A NaN anywhere in a window is that window's max, on both
+  paths.  On the kernels a pixel whose pooled row has a NaN or an infinite
+  element (a window of all -inf too) is NaN throughout, in the output and in its
+  four pixels of `dx`, and no other pixel is touched."""
+  return _stage('pool_norm_act', True, x, scale, shift, impl, act, eps, fused)
+
+
+def norm_act_upsample(x, scale=None, shift=None, impl='rms', act='silu', eps=1e-4, fused=None):
+  """The tail of a `Decoder` stage (dreamerv3/rssm.py:327, 336-338, 346):
+  `act(Norm(x))` and then every pixel repeated 2x2, which feeds the next `Conv2D`.
+  `x` is a CUDA tensor (..., H, W, C), channels last, float32 or bfloat16; the
+  result is (..., 2H, 2W, C) with `out[..., 2h+i, 2w+j, :] = act(Norm(x))[..., h, w, :]`
+  for i, j in {0, 1}, differentiable once with respect to `x`, `scale` and `shift`.
+  Everything else as `pool_norm_act`.
+
+  Composed: `norm_act`'s composed path, then `.repeat_interleave(2, -2)
+  .repeat_interleave(2, -3)` (jnp's `repeat`; torch's `Tensor.repeat` would tile).
+  Fused is `emb_norm_act_upsample` / `emb_norm_act_upsample_grad`, 1 .. 1024
+  channels and at most 2^31 - 1 elements of the result: ONE launch forward that
+  reads a row once and writes its four copies; backward ONE launch that adds the
+  four rows of the incoming gradient in float32, in the fixed order
+  ((0,0) + (0,1)) + ((1,0) + (1,1)), and forms `norm_act`'s gradient from the sum,
+  two with a gradient for `scale` or `shift`."""
+  return _stage('norm_act_upsample', False, x, scale, shift, impl, act, eps, fused)
+
+
+class PoolNormAct(NormAct):
+  """`pool_norm_act` with the norm's parameters: `NormAct` over `units` channels
+  behind a 2x2 max pool (dreamerv3/rssm.py:238-241)."""
+
+  def forward(self, x):
+    return pool_norm_act(x, self.scale, self.shift, self.impl, self.act, self.eps, self.fused)
+
+
+class NormActUpsample(NormAct):
+  """`norm_act_upsample` with the norm's parameters: `NormAct` over `units`
+  channels in front of a 2x2 repeat (dreamerv3/rssm.py:327, 336-338, 346)."""
+
+  def forward(self, x):
+    return norm_act_upsample(x, self.scale, self.shift, self.impl, self.act, self.eps, self.fused)
 
 
 def _composed_gru_gate(x, deter, blocks):

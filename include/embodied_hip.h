@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports (162 functions). */
+ * it exports (167 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -54,8 +54,10 @@ extern "C" {
  * emb_normal_sample, emb_philox_normal, emb_normal_policy_launches,
  * emb_block_linear_plan, emb_stat_rows, emb_stat_rows_launches, emb_mean_fill,
  * emb_optim_grad_norms, emb_optim_adam_update, emb_slow_table, emb_slow_update,
- * emb_optim_update_slow, emb_optim_adam_update_slow
- * (additions only).                                                          */
+ * emb_optim_update_slow, emb_optim_adam_update_slow, emb_pool_norm_act,
+ * emb_pool_norm_act_grad, emb_norm_act_upsample, emb_norm_act_upsample_grad,
+ * emb_conv_stage_launches
+ * (additions only).                                                         */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -955,6 +957,58 @@ int32_t emb_norm_act_grad(const void* x, const void* scale, const void* shift, c
 /* Kernel launches the two entry points above have issued in this process,
  * counted where the kernels are launched.                                      */
 int32_t emb_norm_act_launches(int64_t* count);
+
+/* ---- the tails of the convolution stages: pool + Norm + act, Norm + act + upsample
+ * Encoder.__call__, dreamerv3/rssm.py:238-241 (the default, strided = False):
+ * after the stage's Conv2D a 2x2 max pool (rssm.py:239-240), Norm and act
+ * (rssm.py:241).  Decoder.__call__, dreamerv3/rssm.py:327, 336-338, 346: act(Norm)
+ * and then every pixel repeated 2x2 (rssm.py:336, jnp's element-by-element
+ * repeat) in front of the next Conv2D.  Norm and act are embodied/jax/nets.py:361-399
+ * and embodied/jax/nets.py:26-39, with emb_norm_act's impl, act, eps, scale and
+ * shift and its float32 arithmetic, rounded once at the store.  Tensors are
+ * channels last, contiguous on device, EMB_F32 or EMB_BF16; `x` is (images, H, W, C).
+ *   emb_pool_norm_act        out (images, H/2, W/2, C) = act(Norm(max of the 2x2
+ *                            window)), one launch.  The max propagates a NaN.
+ *   emb_pool_norm_act_grad   gout as out, dx as x: the pooled row and its
+ *                            statistics recomputed from x, its gradient g formed
+ *                            as emb_norm_act_grad does, and per window and channel
+ *                            g / count where x equals the max (count: how many of
+ *                            the four do) and 0 elsewhere.
+ *   emb_norm_act_upsample    out (images, 2H, 2W, C), out[n, 2h+i, 2w+j] =
+ *                            act(Norm(x[n, h, w])) for i, j in {0, 1}; one launch,
+ *                            x read once, four rows written.
+ *   emb_norm_act_upsample_grad  gout as out, dx as x: the four rows of gout added
+ *                            in float32 as ((0,0) + (0,1)) + ((1,0) + (1,1)), then
+ *                            emb_norm_act_grad's row.
+ * dscale, dshift, partials as emb_norm_act_grad: with either, every workgroup
+ * leaves its column sums in `partials` (at least 2 * P * C float32, P =
+ * min(ceil(pixels / (256 / L)), 1024) with pixels = images * H/2 * W/2 for the
+ * pool and images * H * W for the upsample, L = 8, 16, 32, 64 lanes per pixel for
+ * C <= 64, 128, 256, 1024) and a second launch adds them in a fixed order.
+ * No atomics: the same bits run to run.  A pixel whose (pooled) row has a NaN
+ * or infinite mean(x^2) is NaN throughout in out and in its window of dx and
+ * touches no other pixel; dscale and dshift sum over it.
+ * EMB_ERR_INVALID before any launch: an unknown dtype, impl or act, images < 0,
+ * H or W below 1, for the pool an odd H or W, C outside 1 .. 1024, more than
+ * 2^31 - 1 elements in the larger tensor, a negative or non-finite eps, and with
+ * images > 0 a NULL x, out or gout, no output at all, or partials that are NULL
+ * or too small.  images = 0: EMB_OK, nothing is launched or written.           */
+int32_t emb_pool_norm_act(const void* x, const void* scale, const void* shift, int32_t dtype, int64_t images, int64_t H,
+                          int64_t W, int64_t C, int32_t impl, int32_t act, float eps, void* out, void* stream);
+int32_t emb_pool_norm_act_grad(const void* x, const void* scale, const void* shift, const void* gout, int32_t dtype,
+                               int64_t images, int64_t H, int64_t W, int64_t C, int32_t impl, int32_t act, float eps,
+                               void* dx, void* dscale, void* dshift, void* partials, int64_t partial_floats,
+                               void* stream);
+int32_t emb_norm_act_upsample(const void* x, const void* scale, const void* shift, int32_t dtype, int64_t images,
+                              int64_t H, int64_t W, int64_t C, int32_t impl, int32_t act, float eps, void* out,
+                              void* stream);
+int32_t emb_norm_act_upsample_grad(const void* x, const void* scale, const void* shift, const void* gout,
+                                   int32_t dtype, int64_t images, int64_t H, int64_t W, int64_t C, int32_t impl,
+                                   int32_t act, float eps, void* dx, void* dscale, void* dshift, void* partials,
+                                   int64_t partial_floats, void* stream);
+/* Kernel launches the four entry points above have issued in this process,
+ * counted where the kernels are launched.                                      */
+int32_t emb_conv_stage_launches(int64_t* count);
 
 /* ---- the blocked GRU gate of the RSSM, float32 arithmetic on device
  * The tail of RSSM._core, dreamerv3/rssm.py:152-159: `x` (rows, 3 * deter) is what
