@@ -41,6 +41,9 @@ import sys
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
+from tools import pathbench  # noqa: E402
+from tools.pathbench import COPY_CEILING_GBS  # noqa: E402
+
 LIMITS = {'small': 240, 'ppo': 300, 'dreamer': 540}       # seconds per configuration, start-up included
 CLIP = 10.0
 
@@ -49,8 +52,7 @@ def measure(name, kind, args):
   """One configuration, in this process: prints its rows and a `verdict` line."""
   import torch
   from embodied_amd import optim
-  from tools.bench_optim import host_us, parameter_sets
-  from tools.bench_twohot import COPY_CEILING_GBS, device_us
+  from tools.bench_optim import parameter_sets
   assert torch.cuda.is_available(), 'bench_adam needs a GPU'
   shapes = dict(parameter_sets())[name]
   count = sum(math.prod(s) for s in shapes)
@@ -79,25 +81,17 @@ def measure(name, kind, args):
     steps['torch'] = torch_step
   except Exception as e:                                  # reported as what it is, not as a figure
     refused = f'{type(e).__name__}: {str(e).splitlines()[0][:240]}'
-  calls, rounds, host = {}, {k: [] for k in steps}, {}
-  for k, step in steps.items():                           # warm-up; sizes the rounds
-    device_us(step, 2)
-    estimate = device_us(step, 3)
-    calls[k] = int(min(args.calls, max(3, 0.1e6 / estimate)))
-  for _ in range(args.rounds):
-    for k, step in steps.items():
-      rounds[k].append(device_us(step, calls[k]))
-  for k, step in steps.items():
-    host[k] = statistics.median(host_us(step, calls[k]) for _ in range(3))
+  got = pathbench.measure(steps, args.calls, args.rounds, warmup=(2, 3), floor=3)
+  host = {k: statistics.median(pathbench.host_us(step, got[k].calls, sync=False) for _ in range(3))
+          for k, step in steps.items()}
   plan = opts['fused']._plan
   assert opts['fused'].table_uploads == 1
-  median = {k: statistics.median(v) for k, v in rounds.items()}
+  median = {k: v.median for k, v in got.items()}
   row = f'{name} {kind}'
-  print(f'device: {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), '
-        f'torch {torch.__version__}')
+  print('device: ' + pathbench.device_line()[2:])
   print(f'row:   {row}: {count} parameters in {len(shapes)} tensors, {plan["n_chunks"]} chunks of {optim.CHUNK}')
   for k in steps:
-    print(f'row:     {k:<10}{median[k]:10.1f} us [{min(rounds[k]):.1f} .. {max(rounds[k]):.1f}] ({calls[k]})'
+    print(f'row:     {k:<10}{pathbench.cell(got[k].values, got[k].calls, 10, " us")}'
           f'   host {host[k]:8.1f} us')
   if refused:
     print(f'row:     torch     not measured: {refused}')
@@ -120,14 +114,12 @@ def main():
   if args.child:
     measure(args.child[0], args.child[1], args)
     return
-  lines = [
-      f'# tools/bench_adam.py --calls {args.calls} --rounds {args.rounds}',
-      None,                                               # the device, from the first configuration
+  report = pathbench.Report('bench_adam.py', args, None, [      # the device: from the first configuration
       f'# Adam(lr=3e-4, clip={CLIP:g}, eps=1e-7, wd=0), the global norm above the clip; one step()',
       '# us: time between device events over back-to-back steps, per step: median of rounds [min .. max] (steps per round)',
       '# host us: wall time up to the last enqueue, per step',
       '# torch: torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW(fused=True) at the same commit, on tensors of its own',
-  ]
+  ])
   verdicts = []
   for name in args.sets.split(','):
     for kind in ('f32', 'bf16'):
@@ -141,22 +133,17 @@ def main():
         sys.stderr.write(done.stderr[-4000:])
         sys.exit(f'bench_adam: {name} {kind} failed with status {done.returncode}; stopping, nothing written')
       for line in done.stdout.splitlines():
-        if line.startswith('device: ') and lines[1] is None:
-          lines[1] = '# ' + line[len('device: '):]
+        if line.startswith('device: ') and report.lines[1] is None:
+          report.lines[1] = '# ' + line[len('device: '):]
         elif line.startswith('row: '):
-          lines.append(line[len('row: '):])
-          print(lines[-1], flush=True)
+          report.add(line[len('row: '):])
         elif line.startswith('verdict: '):
           verdicts.append(line[len('verdict: '):].split('|'))
   for title, column in (('composed', 1), ('torch', 2)):
-    wins = [v[0] for v in verdicts if v[column] == 'below']
-    losses = [v[0] for v in verdicts if v[column] == 'not below']
-    lines.append(f'# fused median below the {title} median at: ' + (', '.join(wins) or 'no measured row'))
-    lines.append(f'# fused median not below the {title} median at: ' + (', '.join(losses) or 'no measured row'))
-  print('\n'.join(lines[-4:]), flush=True)
-  out = pathlib.Path(args.out)
-  out.parent.mkdir(parents=True, exist_ok=True)
-  out.write_text('\n'.join(line for line in lines if line is not None) + '\n')
+    report.closing(f'fused median below the {title} median at', f'fused median not below the {title} median at',
+                   wins=[v[0] for v in verdicts if v[column] == 'below'],
+                   losses=[v[0] for v in verdicts if v[column] == 'not below'])
+  report.write()
 
 
 if __name__ == '__main__':

@@ -34,7 +34,6 @@ Needs a GPU: there is no CPU fallback and no figure without one.
 """
 import argparse
 import pathlib
-import statistics
 import sys
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
@@ -42,12 +41,20 @@ sys.path.insert(0, str(ROOT))
 
 import torch  # noqa: E402
 
-from tools.bench_twohot import COPY_CEILING_GBS, device_us  # noqa: E402
+from tools import pathbench  # noqa: E402
+from tools.pathbench import COPY_CEILING_GBS  # noqa: E402
 
 POOL_SHAPES = [(64, 64, 128), (32, 32, 192), (16, 16, 256), (8, 8, 256), (64, 64, 32)]
 UPSAMPLE_SHAPES = [(4, 4, 256), (8, 8, 256), (16, 16, 192), (32, 32, 128)]
 FRAMES = (16, 1024)
 PATHS = ('composed', 'parent', 'fused')
+
+
+def row(name, piece, got, moved):
+  """One line of the file: the `pathbench.Rounds` of every path, the bytes the fused call moves."""
+  rate = moved / got['fused'].median / 1e3
+  return (f'  {name:<34}{piece:<9}{got["composed"].cell:<32}{got["parent"].cell:<32}{got["fused"].cell:<32}'
+          f'{rate:.0f} = {rate / COPY_CEILING_GBS:.2f} of the ceiling')
 
 
 def main():
@@ -59,38 +66,20 @@ def main():
   assert torch.cuda.is_available(), 'bench_conv_stage needs a GPU'
   from embodied_amd import nets
 
-  lines = [
-      f'# tools/bench_conv_stage.py --calls {args.calls} --rounds {args.rounds}',
-      f'# {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), torch {torch.__version__}'
-      '; nets.pool_norm_act and nets.norm_act_upsample (rms, silu, scale with a gradient)',
+  device = pathbench.device_line() + '; nets.pool_norm_act and nets.norm_act_upsample (rms, silu, scale with a gradient)'
+  report = pathbench.Report('bench_conv_stage.py', args, device, [
       '# shape: x as N x H x W x C; parent: amax + norm_act(fused=True), norm_act(fused=True) + repeat_interleave',
       '# us: time between device events over back-to-back calls, per call: median of rounds [min .. max] (calls per round)',
       f'# GB/s: bytes the fused call must move / its median time; copy ceiling {COPY_CEILING_GBS:.0f} GB/s (read + write)',
       f'# {"shape":<34}{"piece":<9}{"composed us":<32}{"parent us":<32}{"fused us":<32}fused GB/s',
-  ]
-  print('\n'.join(lines), flush=True)
+  ])
   gen = torch.Generator(device='cuda').manual_seed(0)
-  wins, losses = [], []
 
   def measure(name, pieces, moved):
     for piece in ('forward', 'fwd+bwd'):
-      calls, rounds = {}, {path: [] for path in PATHS}
-      for path in PATHS:                               # warm-up of this shape; sizes the rounds
-        device_us(pieces[path][piece], 3)
-        estimate = device_us(pieces[path][piece], 5)
-        calls[path] = int(min(args.calls, max(5, 0.1e6 / estimate)))
-      for _ in range(args.rounds):
-        for path in PATHS:
-          rounds[path].append(device_us(pieces[path][piece], calls[path]))
-      median = {path: statistics.median(rounds[path]) for path in PATHS}
-      cell = lambda p: f'{median[p]:9.1f} [{min(rounds[p]):.1f} .. {max(rounds[p]):.1f}] ({calls[p]})'
-      below = median['fused'] < median['composed'] and median['fused'] < median['parent']
-      (wins if below else losses).append(f'{name} {piece}')
-      rate = moved[piece] / median['fused'] / 1e3
-      line = (f'  {name:<34}{piece:<9}{cell("composed"):<32}{cell("parent"):<32}{cell("fused"):<32}'
-              f'{rate:.0f} = {rate / COPY_CEILING_GBS:.2f} of the ceiling')
-      lines.append(line)
-      print(line, flush=True)
+      got = pathbench.measure({path: pieces[path][piece] for path in PATHS}, args.calls, args.rounds)
+      report.verdict(f'{name} {piece}', pathbench.median_below(got['fused'], got['composed'], got['parent']))
+      report.add(row(name, piece, got, moved[piece]))
 
   for stage, shapes in (('pool', POOL_SHAPES), ('upsample', UPSAMPLE_SHAPES)):
     call = nets.pool_norm_act if stage == 'pool' else nets.norm_act_upsample
@@ -129,12 +118,8 @@ def main():
           del x, gout, pieces, forwards
           torch.cuda.empty_cache()
 
-  lines.append('# fused median below both rivals at: ' + (', '.join(wins) or 'no measured row'))
-  lines.append('# fused median not below both rivals at: ' + (', '.join(losses) or 'no measured row'))
-  print('\n'.join(lines[-2:]), flush=True)
-  out = pathlib.Path(args.out)
-  out.parent.mkdir(parents=True, exist_ok=True)
-  out.write_text('\n'.join(lines) + '\n')
+  report.closing('fused median below both rivals at', 'fused median not below both rivals at')
+  report.write()
 
 
 if __name__ == '__main__':

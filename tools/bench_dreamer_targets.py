@@ -31,9 +31,7 @@ Needs a GPU: there is no CPU fallback and no figure without one.
 """
 import argparse
 import pathlib
-import statistics
 import sys
-import time
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
@@ -41,33 +39,11 @@ sys.path.insert(0, str(ROOT))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from tools import pathbench  # noqa: E402
+from tools.pathbench import host_us  # noqa: E402
+
 SHAPES = [(16, 16), (256, 16), (1024, 16), (1024, 17), (16, 1024), (4096, 16)]   # the last: composed (and parent) only
 LAM = 0.95
-
-
-def timed(call, calls):
-  torch.cuda.synchronize()
-  start = time.perf_counter()
-  for _ in range(calls):
-    call()
-  torch.cuda.synchronize()
-  return (time.perf_counter() - start) / calls * 1e6
-
-
-def device_ops(call, calls=5):
-  """Device-side events per call as torch.profiler sees them (None: no profiler)."""
-  try:
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-      for _ in range(calls):
-        call()
-      torch.cuda.synchronize()
-    events = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
-    return len(events) / calls
-  except Exception as e:      # a figure that was not measured is reported as such
-    print(f'# torch.profiler window failed: {e!r}', file=sys.stderr)
-    return None
 
 
 def parent_chain(rew, con, pred, retnorm, valnorm, advnorm, disc=1.0, lam=LAM):
@@ -100,16 +76,14 @@ def main():
   from embodied_amd import scans
 
   names = ('parent', 'composed', 'fused')
-  lines = [
-      f'# tools/bench_dreamer_targets.py --calls {args.calls} --rounds {args.rounds}',
-      f'# {torch.cuda.get_device_name(0)}, torch {torch.__version__}; imag_loss:397-419 with update, '
-      "retnorm 'perc', valnorm and advnorm 'none', float32 contiguous inputs",
+  device = (pathbench.device_line(arch=False) + '; imag_loss:397-419 with update, '
+            "retnorm 'perc', valnorm and advnorm 'none', float32 contiguous inputs")
+  report = pathbench.Report('bench_dreamer_targets.py', args, device, [
       '# us/call: median of rounds [min .. max], host clock over back-to-back calls + synchronise; (calls per round)',
       '# launches: device operations per call (torch.profiler window)',
       f'# {"shape":<11}{"returns":<9}' + ''.join(f'{name + " us/call":<38}' for name in names)
       + 'launches parent / composed / fused',
-  ]
-  print('\n'.join(lines), flush=True)
+  ])
   gen = np.random.default_rng(0)
   wins, losses = [], []
   for N, T in SHAPES:
@@ -136,45 +110,25 @@ def main():
         assert torch.allclose(a, b, rtol=1e-4, atol=1e-4), (N, T, name)
     calls = {}
     for name, call in paths.items():                # warm-up of this shape; sizes the rounds
-      timed(call, 3)
-      estimate = timed(call, 10)
-      calls[name] = int(min(args.calls, max(5, 0.3e6 / estimate)))
-      timed(call, max(calls[name] // 10, 1))
-    rounds = {name: [] for name in paths}
-    for _ in range(args.rounds):
-      for name in rounds:
-        rounds[name].append(timed(paths[name], calls[name]))
-    seen = {name: None if args.no_profiler else device_ops(paths[name]) for name in rounds}
-
-    def cell(name):
-      if name not in rounds:
-        return 'does not fit one workgroup'
-      values = rounds[name]
-      return f'{statistics.median(values):9.1f} [{min(values):.1f} .. {max(values):.1f}] ({calls[name]})'
-
-    def count(name):
-      if name not in rounds:
-        return '-'
-      return 'not measured' if seen[name] is None else f'{seen[name]:.1f}'
-
-    if 'fused' in rounds:
-      if max(rounds['fused']) < min(rounds['composed']):
+      calls[name] = pathbench.sized(call, args.calls, warmup=(3, 10), budget_us=0.3e6, timer=host_us)
+      host_us(call, max(calls[name] // 10, 1))
+    got = pathbench.run_rounds(paths, calls, args.rounds, timer=host_us)
+    seen = {name: None if args.no_profiler else pathbench.device_ops(paths[name], 5) for name in got}
+    cell = lambda name: got[name].cell if name in got else 'does not fit one workgroup'
+    count = lambda name: pathbench.count(seen[name]) if name in got else '-'
+    if 'fused' in got:
+      if pathbench.every_round_below(got['fused'], got['composed']):
         wins.append((N, T))
-      elif statistics.median(rounds['fused']) >= statistics.median(rounds['composed']):
+      elif not pathbench.median_below(got['fused'], got['composed']):
         losses.append((N, T))
-    line = (f'  {f"{N}x{T}":<11}{N * (T - 1):<9}' + ''.join(f'{cell(name):<38}' for name in names)
-            + ' / '.join(count(name) for name in names))
-    lines.append(line)
-    print(line, flush=True)
+    report.add(f'  {f"{N}x{T}":<11}{N * (T - 1):<9}' + ''.join(f'{cell(name):<38}' for name in names)
+               + ' / '.join(count(name) for name in names))
   largest = max(wins, key=lambda shape: shape[0] * (shape[1] - 1)) if wins else None
-  lines.append('# fused beats composed, every round of one below every round of the other, at: '
-               + (', '.join(f'{n}x{t}' for n, t in wins) or 'no measured shape')
-               + (f'; largest: {largest[0]}x{largest[1]} = {largest[0] * (largest[1] - 1)} returns' if largest else ''))
-  lines.append('# fused does not beat composed (median) at: ' + (', '.join(f'{n}x{t}' for n, t in losses) or 'no measured shape'))
-  print('\n'.join(lines[-2:]), flush=True)
-  out = pathlib.Path(args.out)
-  out.parent.mkdir(parents=True, exist_ok=True)
-  out.write_text('\n'.join(lines) + '\n')
+  report.add('# fused beats composed, every round of one below every round of the other, at: '
+             + (', '.join(f'{n}x{t}' for n, t in wins) or 'no measured shape')
+             + (f'; largest: {largest[0]}x{largest[1]} = {largest[0] * (largest[1] - 1)} returns' if largest else ''),
+             '# fused does not beat composed (median) at: ' + (', '.join(f'{n}x{t}' for n, t in losses) or 'no measured shape'))
+  report.write()
 
 
 if __name__ == '__main__':

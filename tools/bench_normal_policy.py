@@ -37,7 +37,6 @@ import argparse
 import pathlib
 import statistics
 import sys
-import time
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
@@ -45,21 +44,21 @@ sys.path.insert(0, str(ROOT))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from tools.bench_twohot import COPY_CEILING_GBS, device_ops, device_us  # noqa: E402
+from tools import pathbench  # noqa: E402
+from tools.pathbench import COPY_CEILING_GBS  # noqa: E402
 
 SHAPES = [(n, 16, actions, kind) for n in (1024, 16384) for actions in (1, 6, 21, 38) for kind in ('f32', 'bf16')]
 KIND, MINSTD, MAXSTD, ACTENT = 'bounded', 0.1, 1.0, 3e-4
 
 
-def enqueue_us(fn, calls):
-  """Host time per call of issuing `calls` calls; the device is waited for outside the clock."""
-  torch.cuda.synchronize()
-  start = time.perf_counter()
-  for _ in range(calls):
-    fn()
-  stop = time.perf_counter()
-  torch.cuda.synchronize()
-  return (stop - start) * 1e6 / calls
+def row(name, piece, composed, fused, enqueue, ops, moved):
+  """One line of the file: the two paths' `pathbench.Rounds`, the fused call's enqueue time (median of the rounds),
+  the operation counts, the bytes the fused call moves."""
+  rate = moved / fused.median / 1e3
+  bound = f'{enqueue:.1f}' + (' host' if fused.median <= 1.15 * enqueue else '')
+  counts = pathbench.count(ops[0]) + ' / ' + pathbench.count(ops[1])
+  return (f'  {name:<22}{piece:<10}{composed.cell:<34}{fused.cell:<34}{bound:<14}'
+          f'{counts:<22}{rate:.0f} = {rate / COPY_CEILING_GBS:.2f} of the ceiling')
 
 
 def main():
@@ -72,20 +71,17 @@ def main():
   assert torch.cuda.is_available(), 'bench_normal_policy needs a GPU'
   from embodied_amd import outs
 
-  lines = [
-      f'# tools/bench_normal_policy.py --calls {args.calls} --rounds {args.rounds}',
-      f'# {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), torch {torch.__version__}'
-      f'; outs.normal_policy_loss / Normal.sample, {KIND} ({MINSTD}, {MAXSTD}), actent {ACTENT}, drop_last, weight (N, T)',
+  device = (pathbench.device_line() + f'; outs.normal_policy_loss / Normal.sample, {KIND} ({MINSTD}, {MAXSTD}), '
+            f'actent {ACTENT}, drop_last, weight (N, T)')
+  report = pathbench.Report('bench_normal_policy.py', args, device, [
       '# shape: N x T x A',
       '# us: time between device events over back-to-back calls, per call: median of rounds [min .. max] (calls per round)',
       '# enqueue: host time per fused call without waiting for the device; `host`: the fused us is the enqueue time',
       '# ops: device operations per call (torch.profiler window), composed / fused',
       f'# GB/s: bytes the fused call must move / its median time; copy ceiling {COPY_CEILING_GBS:.0f} GB/s (read + write)',
       f'# {"shape":<22}{"piece":<10}{"composed us":<34}{"fused us":<34}{"enqueue us":<14}{"ops composed / fused":<22}fused GB/s',
-  ]
-  print('\n'.join(lines), flush=True)
+  ])
   gen = np.random.default_rng(0)
-  wins, losses = [], []
   for n, t, actions, kind in SHAPES:
     dtype = torch.float32 if kind == 'f32' else torch.bfloat16
     shape = (n, t, actions)
@@ -121,35 +117,14 @@ def main():
     name = 'x'.join(str(s) for s in shape) + ' ' + kind
     moves = (('forward', inputs + 4 * count), ('fwd+bwd', 2 * (inputs + 4 * count) + inputs), ('sample', inputs + 4 * count))
     for piece, moved in moves:
-      def timed(fused, calls):
-        return device_us(pieces[fused][piece], calls)
-      calls, rounds, issue = {}, {False: [], True: []}, []
-      for fused in rounds:                             # warm-up of this shape; sizes the rounds
-        timed(fused, 3)
-        estimate = timed(fused, 5)
-        calls[fused] = int(min(args.calls, max(5, 0.1e6 / estimate)))
-      for _ in range(args.rounds):
-        for fused in rounds:
-          rounds[fused].append(timed(fused, calls[fused]))
-        issue.append(enqueue_us(pieces[True][piece], calls[True]))
-      ops = {f: None if args.no_profiler else device_ops(pieces[f][piece]) for f in rounds}
-      median = {f: statistics.median(rounds[f]) for f in rounds}
-      enqueue = statistics.median(issue)
-      cell = lambda f: f'{median[f]:9.1f} [{min(rounds[f]):.1f} .. {max(rounds[f]):.1f}] ({calls[f]})'
-      number = lambda f: 'not measured' if ops[f] is None else f'{ops[f]:.1f}'
-      (wins if median[True] < median[False] else losses).append(f'{name} {piece}')
-      rate = moved / median[True] / 1e3
-      bound = f'{enqueue:.1f}' + (' host' if median[True] <= 1.15 * enqueue else '')
-      line = (f'  {name:<22}{piece:<10}{cell(False):<34}{cell(True):<34}{bound:<14}'
-              f'{number(False) + " / " + number(True):<22}{rate:.0f} = {rate / COPY_CEILING_GBS:.2f} of the ceiling')
-      lines.append(line)
-      print(line, flush=True)
-  lines.append('# fused median below composed median at: ' + (', '.join(wins) or 'no measured row'))
-  lines.append('# fused median not below composed median at: ' + (', '.join(losses) or 'no measured row'))
-  print('\n'.join(lines[-2:]), flush=True)
-  out = pathlib.Path(args.out)
-  out.parent.mkdir(parents=True, exist_ok=True)
-  out.write_text('\n'.join(lines) + '\n')
+      paths, issue = {f: pieces[f][piece] for f in (False, True)}, []
+      enqueue = lambda calls: issue.append(pathbench.host_us(paths[True], calls[True], sync=False))
+      got = pathbench.measure(paths, args.calls, args.rounds, after_round=enqueue)
+      ops = [None if args.no_profiler else pathbench.device_ops(paths[f]) for f in paths]
+      report.verdict(f'{name} {piece}', pathbench.median_below(got[True], got[False]))
+      report.add(row(name, piece, got[False], got[True], statistics.median(issue), ops, moved))
+  report.closing()
+  report.write()
 
 
 if __name__ == '__main__':

@@ -34,7 +34,6 @@ Needs a GPU: there is no CPU fallback and no figure without one.
 import argparse
 import itertools
 import pathlib
-import statistics
 import sys
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
@@ -43,7 +42,7 @@ sys.path.insert(0, str(ROOT))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from tools.bench_twohot import device_ops, device_us  # noqa: E402
+from tools import pathbench  # noqa: E402
 
 # the RSSM's observe step, its imagination step, a large batch, the actor's head, and
 # the switch-over from one segment of 64 lanes to two values per lane (64 | 65 classes)
@@ -72,19 +71,16 @@ def main():
   assert torch.cuda.is_available(), 'bench_onehot_sample needs a GPU'
   from embodied_amd import _lib, outs
 
-  lines = [
-      f'# tools/bench_onehot_sample.py --calls {args.calls} --rounds {args.rounds}',
-      f'# {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), torch {torch.__version__}'
-      f'; outs.OneHot.sample, unimix {UNIMIX}, a new offset every call',
+  device = pathbench.device_line() + f'; outs.OneHot.sample, unimix {UNIMIX}, a new offset every call'
+  report = pathbench.Report('bench_onehot_sample.py', args, device, [
       '# shape: rows x groups x classes',
       '# us: time between device events over back-to-back calls, per call: median of rounds [min .. max] (calls per round)',
       '# entry: emb_onehot_sample alone through the binding, buffers made once (forward rows only)',
       '# ops: device operations per call (torch.profiler window), composed / fused / multinomial',
       f'# {"shape":<22}{"piece":<10}{"composed us":<32}{"fused us":<32}{"multinomial us":<32}{"entry us":<10}ops',
-  ]
-  print('\n'.join(lines), flush=True)
+  ])
   gen = np.random.default_rng(0)
-  wins, losses, medians = [], [], {}
+  medians = {}
   for rows, groups, classes in SHAPES:
     for kind in ('f32', 'bf16'):
       dtype = torch.float32 if kind == 'f32' else torch.bfloat16
@@ -114,45 +110,29 @@ def main():
           None, None, onehot.data_ptr(), stream)
       name = 'x'.join(str(s) for s in shape) + ' ' + kind
       for piece in ('forward', 'fwd+bwd'):
-        def timed(path, calls):
-          return device_us(entry if path == 'entry' else pieces[path][piece], calls)
-        paths = PATHS + (('entry',) if piece == 'forward' else ())
-        calls, rounds = {}, {path: [] for path in paths}
-        for path in paths:                               # warm-up of this shape; sizes the rounds
-          timed(path, 3)
-          estimate = timed(path, 5)
-          calls[path] = int(min(args.calls, max(5, 0.1e6 / estimate)))
-        for _ in range(args.rounds):
-          for path in paths:
-            rounds[path].append(timed(path, calls[path]))
-        ops = {p: None if args.no_profiler else device_ops(pieces[p][piece]) for p in PATHS}
-        median = {p: statistics.median(rounds[p]) for p in paths}
-        medians[name, piece] = median
-        cell = lambda p: f'{median[p]:9.1f} [{min(rounds[p]):.1f} .. {max(rounds[p]):.1f}] ({calls[p]})'
-        count = lambda p: 'not measured' if ops[p] is None else f'{ops[p]:.1f}'
-        (wins if median['fused'] < median['composed'] else losses).append(f'{name} {piece}')
+        paths = {path: pieces[path][piece] for path in PATHS}
+        if piece == 'forward':
+          paths['entry'] = entry
+        got = pathbench.measure(paths, args.calls, args.rounds)
+        ops = [None if args.no_profiler else pathbench.device_ops(paths[p]) for p in PATHS]
+        median = medians[name, piece] = {p: got[p].median for p in paths}
+        report.verdict(f'{name} {piece}', pathbench.median_below(got['fused'], got['composed']))
         alone = f'{median["entry"]:.1f}' if 'entry' in median else '-'
-        line = (f'  {name:<22}{piece:<10}{cell("composed"):<32}{cell("fused"):<32}{cell("multinomial"):<32}'
-                f'{alone:<10}{" / ".join(count(p) for p in PATHS)}')
-        lines.append(line)
-        print(line, flush=True)
-  lines.append('# fused median below composed median at: ' + (', '.join(wins) or 'no measured row'))
-  lines.append('# fused median not below composed median at: ' + (', '.join(losses) or 'no measured row'))
+        report.add(f'  {name:<22}{piece:<10}{got["composed"].cell:<32}{got["fused"].cell:<32}{got["multinomial"].cell:<32}'
+                   f'{alone:<10}{" / ".join(pathbench.count(n) for n in ops)}')
+  report.closing()
   small, large = medians['16x32x32 f32', 'forward'], medians['1024x32x32 f32', 'forward']
   bound = small['fused'] > 2 * small['entry'] and small['fused'] > 0.8 * large['fused']
-  lines.append(
+  report.add(
       f'# 16 rows against 1024 at 32 x 32 f32, forward: fused {small["fused"]:.1f} / {large["fused"]:.1f} us, the entry '
       f'point alone {small["entry"]:.1f} / {large["entry"]:.1f} us: the fused call at 16 rows is '
       + ('bound by the host\'s enqueue (the facade and the launch), not by the kernel' if bound else
          'not bound by the host\'s enqueue by this measure'))
   a, b = medians['1024x32x64 f32', 'forward'], medians['1024x32x65 f32', 'forward']
-  lines.append(f'# the switch-over at 64 | 65 classes (one segment | two values per lane), 1024 x 32, f32 forward: '
-               f'fused {a["fused"]:.1f} | {b["fused"]:.1f} us, entry {a["entry"]:.1f} | {b["entry"]:.1f} us; '
-               'the narrower switch-overs (2 .. 32 lanes) were not measured')
-  print('\n'.join(lines[-4:]), flush=True)
-  out = pathlib.Path(args.out)
-  out.parent.mkdir(parents=True, exist_ok=True)
-  out.write_text('\n'.join(lines) + '\n')
+  report.add(f'# the switch-over at 64 | 65 classes (one segment | two values per lane), 1024 x 32, f32 forward: '
+             f'fused {a["fused"]:.1f} | {b["fused"]:.1f} us, entry {a["entry"]:.1f} | {b["entry"]:.1f} us; '
+             'the narrower switch-overs (2 .. 32 lanes) were not measured')
+  report.write()
 
 
 if __name__ == '__main__':

@@ -35,7 +35,6 @@ import math
 import pathlib
 import statistics
 import sys
-import time
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
@@ -43,7 +42,8 @@ sys.path.insert(0, str(ROOT))
 import torch  # noqa: E402
 
 from tools import count_params  # noqa: E402
-from tools.bench_twohot import COPY_CEILING_GBS, device_us  # noqa: E402
+from tools import pathbench  # noqa: E402
+from tools.pathbench import COPY_CEILING_GBS, device_us, host_us  # noqa: E402
 
 
 class Counted(int):
@@ -97,35 +97,6 @@ def parameter_sets():
   return (('small', small), ('ppo', ppo), ('dreamer', dreamer))
 
 
-def device_ops(call, calls=3):
-  """Device-side operations per call as torch.profiler sees them (None: no
-  profiler).  `Optimizer.step` runs inside a profiler annotation that shows up
-  among the device events, one per step: it is no operation and is left out."""
-  try:
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-      for _ in range(calls):
-        call()
-      torch.cuda.synchronize()
-    events = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
-              and not e.name.startswith('Optimizer.step')]
-    return len(events) / calls
-  except Exception as e:      # a figure that was not measured is reported as such
-    print(f'# torch.profiler window failed: {e!r}', file=sys.stderr)
-    return None
-
-
-def host_us(call, calls):
-  torch.cuda.synchronize()
-  start = time.perf_counter()
-  for _ in range(calls):
-    call()
-  spent = time.perf_counter() - start
-  torch.cuda.synchronize()
-  return spent * 1e6 / calls
-
-
 def main():
   parser = argparse.ArgumentParser()
   parser.add_argument('--calls', type=int, default=200)
@@ -137,19 +108,15 @@ def main():
   assert torch.cuda.is_available(), 'bench_optim needs a GPU'
   from embodied_amd import _lib, optim
 
-  lines = [
-      f'# tools/bench_optim.py --calls {args.calls} --rounds {args.rounds}',
-      f'# {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), torch {torch.__version__}'
-      '; LaProp(lr=4e-5, agc=0.3, wd=0), one step()',
+  device = pathbench.device_line() + '; LaProp(lr=4e-5, agc=0.3, wd=0), one step()'
+  report = pathbench.Report('bench_optim.py', args, device, [
       '# us: time between device events over back-to-back steps, per step: median of rounds [min .. max] (steps per round)',
       '# host us: wall time up to the last enqueue, per step; ops: device operations per step (torch.profiler window)',
       f'# ceiling: 36 (float32 gradients) or 32 (bfloat16) bytes per parameter / the fused median; copy ceiling '
       f'{COPY_CEILING_GBS:.0f} GB/s (read + write)',
       '# norms: the norms launch alone, 8 (6) bytes per parameter read; above the copy ceiling = served from the Infinity Cache',
       '# Adam: torch.optim.Adam(fused=True), context only (float32 gradients only: it takes no others)',
-  ]
-  print('\n'.join(lines), flush=True)
-  wins, losses = [], []
+  ])
   torch.manual_seed(0)
   for name, shapes in parameter_sets():
     if name not in args.sets.split(','):
@@ -164,49 +131,36 @@ def main():
       opts = {'composed': optim.LaProp(params, fused=False), 'fused': optim.LaProp(params, fused=True)}
       if kind == 'f32':
         opts['Adam'] = torch.optim.Adam(params, lr=4e-5, fused=True)
-      calls, rounds, host = {}, {k: [] for k in opts}, {}
-      for k, opt in opts.items():                      # warm-up; sizes the rounds
-        device_us(opt.step, 2)
-        estimate = device_us(opt.step, 3)
-        calls[k] = int(min(args.calls, max(3, 0.1e6 / estimate)))
-      for _ in range(args.rounds):
-        for k, opt in opts.items():
-          rounds[k].append(device_us(opt.step, calls[k]))
-      for k, opt in opts.items():
-        host[k] = statistics.median(host_us(opt.step, calls[k]) for _ in range(3))
-      ops = {k: None if args.no_profiler else device_ops(opt.step) for k, opt in opts.items()}
+      steps = {k: opt.step for k, opt in opts.items()}
+      got = pathbench.measure(steps, args.calls, args.rounds, warmup=(2, 3), floor=3)
+      host = {k: statistics.median(host_us(step, got[k].calls, sync=False) for _ in range(3)) for k, step in steps.items()}
+      ops = {k: None if args.no_profiler else pathbench.device_ops(step, skip='Optimizer.step')
+             for k, step in steps.items()}
       plan = opts['fused']._plan
       norms = lambda: _lib.api.emb_optim_norms(plan['table'].data_ptr(), plan['chunks'].data_ptr(), plan['n_chunks'],
                                                plan['partials'].data_ptr(), _lib.raw_stream(plan['device']))
       device_us(norms, 3)
-      norms_us = statistics.median(device_us(norms, max(10, calls['fused'])) for _ in range(args.rounds))
+      norms_us = statistics.median(device_us(norms, max(10, got['fused'].calls)) for _ in range(args.rounds))
       assert opts['fused'].table_uploads == 1
-      median = {k: statistics.median(v) for k, v in rounds.items()}
       row = f'{name} {kind}'
-      lines.append(f'  {row}: {count} parameters in {len(shapes)} tensors, {plan["n_chunks"]} chunks of {optim.CHUNK}')
+      report.add(f'  {row}: {count} parameters in {len(shapes)} tensors, {plan["n_chunks"]} chunks of {optim.CHUNK}')
       for k in opts:
-        shown = 'not measured' if ops[k] is None else f'{ops[k]:.1f}'
-        lines.append(f'    {k:<10}{median[k]:10.1f} us [{min(rounds[k]):.1f} .. {max(rounds[k]):.1f}] ({calls[k]})'
-                     f'   host {host[k]:8.1f} us   ops {shown}')
+        report.add(f'    {k:<10}{pathbench.cell(got[k].values, got[k].calls, 10, " us")}'
+                   f'   host {host[k]:8.1f} us   ops {pathbench.count(ops[k])}')
       per = 36 if kind == 'f32' else 32
-      rate = per * count / median['fused'] / 1e3
+      rate = per * count / got['fused'].median / 1e3
       read = (8 if kind == 'f32' else 6) * count / norms_us / 1e3
-      lines.append(f'    fused: {rate:.0f} GB/s = {rate / COPY_CEILING_GBS:.2f} of the ceiling; norms launch alone '
-                   f'{norms_us:.1f} us = {read:.0f} GB/s read'
-                   f' ({"above the copy ceiling: from the Infinity Cache" if read > COPY_CEILING_GBS else "below the copy ceiling"})')
-      (wins if median['fused'] < median['composed'] else losses).append(row)
-      print('\n'.join(lines[-(len(opts) + 2):]), flush=True)
-      del opts, plan, norms
+      report.add(f'    fused: {rate:.0f} GB/s = {rate / COPY_CEILING_GBS:.2f} of the ceiling; norms launch alone '
+                 f'{norms_us:.1f} us = {read:.0f} GB/s read'
+                 f' ({"above the copy ceiling: from the Infinity Cache" if read > COPY_CEILING_GBS else "below the copy ceiling"})')
+      report.verdict(row, pathbench.median_below(got['fused'], got['composed']))
+      del opts, steps, plan, norms
     for p in params:
       p.grad = None
     del params
     torch.cuda.empty_cache()
-  lines.append('# fused median below composed median at: ' + (', '.join(wins) or 'no measured row'))
-  lines.append('# fused median not below composed median at: ' + (', '.join(losses) or 'no measured row'))
-  print('\n'.join(lines[-2:]), flush=True)
-  out = pathlib.Path(args.out)
-  out.parent.mkdir(parents=True, exist_ok=True)
-  out.write_text('\n'.join(lines) + '\n')
+  report.closing()
+  report.write()
 
 
 if __name__ == '__main__':

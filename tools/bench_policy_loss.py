@@ -27,7 +27,6 @@ Needs a GPU: there is no CPU fallback and no figure without one.
 """
 import argparse
 import pathlib
-import statistics
 import sys
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
@@ -36,11 +35,20 @@ sys.path.insert(0, str(ROOT))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from tools.bench_twohot import COPY_CEILING_GBS, device_ops, device_us  # noqa: E402
+from tools import pathbench  # noqa: E402
+from tools.pathbench import COPY_CEILING_GBS  # noqa: E402
 
 SHAPES = [(n, 16, groups, classes, kind) for n in (1024, 16384) for classes in (6, 18, 256) for groups in (0, 4)
           for kind in ('f32', 'bf16')]
 UNIMIX, ACTENT = 0.0, 3e-4
+
+
+def row(name, piece, composed, fused, ops, moved):
+  """One line of the file: the two paths' `pathbench.Rounds`, their operation counts, the bytes the fused call moves."""
+  rate = moved / fused.median / 1e3
+  counts = pathbench.count(ops[0]) + ' / ' + pathbench.count(ops[1])
+  return (f'  {name:<26}{piece:<10}{composed.cell:<34}{fused.cell:<34}{counts:<22}'
+          f'{rate:.0f} = {rate / COPY_CEILING_GBS:.2f} of the ceiling')
 
 
 def main():
@@ -53,19 +61,15 @@ def main():
   assert torch.cuda.is_available(), 'bench_policy_loss needs a GPU'
   from embodied_amd import outs
 
-  lines = [
-      f'# tools/bench_policy_loss.py --calls {args.calls} --rounds {args.rounds}',
-      f'# {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), torch {torch.__version__}'
-      f'; outs.policy_loss, unimix {UNIMIX}, actent {ACTENT}, drop_last, weight (N, T)',
+  device = pathbench.device_line() + f'; outs.policy_loss, unimix {UNIMIX}, actent {ACTENT}, drop_last, weight (N, T)'
+  report = pathbench.Report('bench_policy_loss.py', args, device, [
       '# shape: N x T x [groups x] classes',
       '# us: time between device events over back-to-back calls, per call: median of rounds [min .. max] (calls per round)',
       '# ops: device operations per call (torch.profiler window), composed / fused',
       f'# GB/s: bytes the fused call must move / its median time; copy ceiling {COPY_CEILING_GBS:.0f} GB/s (read + write)',
       f'# {"shape":<26}{"piece":<10}{"composed us":<34}{"fused us":<34}{"ops composed / fused":<22}fused GB/s',
-  ]
-  print('\n'.join(lines), flush=True)
+  ])
   gen = np.random.default_rng(0)
-  wins, losses = [], []
   for n, t, groups, classes, kind in SHAPES:
     dtype = torch.float32 if kind == 'f32' else torch.bfloat16
     shape = (n, t, groups, classes) if groups else (n, t, classes)
@@ -94,32 +98,13 @@ def main():
     assert torch.allclose(*grads, rtol=1e-4 if kind == 'f32' else 2.0 ** -6, atol=1e-5), (shape, kind, 'grad')
     name = 'x'.join(str(s) for s in shape) + ' ' + kind
     for piece, moved in (('forward', size), ('fwd+bwd', 3 * size)):
-      def timed(fused, calls):
-        return device_us(pieces[fused][piece], calls)
-      calls, rounds = {}, {False: [], True: []}
-      for fused in rounds:                             # warm-up of this shape; sizes the rounds
-        timed(fused, 3)
-        estimate = timed(fused, 5)
-        calls[fused] = int(min(args.calls, max(5, 0.1e6 / estimate)))
-      for _ in range(args.rounds):
-        for fused in rounds:
-          rounds[fused].append(timed(fused, calls[fused]))
-      ops = {f: None if args.no_profiler else device_ops(pieces[f][piece]) for f in rounds}
-      median = {f: statistics.median(rounds[f]) for f in rounds}
-      cell = lambda f: f'{median[f]:9.1f} [{min(rounds[f]):.1f} .. {max(rounds[f]):.1f}] ({calls[f]})'
-      count = lambda f: 'not measured' if ops[f] is None else f'{ops[f]:.1f}'
-      (wins if median[True] < median[False] else losses).append(f'{name} {piece}')
-      rate = moved / median[True] / 1e3
-      line = (f'  {name:<26}{piece:<10}{cell(False):<34}{cell(True):<34}{count(False) + " / " + count(True):<22}'
-              f'{rate:.0f} = {rate / COPY_CEILING_GBS:.2f} of the ceiling')
-      lines.append(line)
-      print(line, flush=True)
-  lines.append('# fused median below composed median at: ' + (', '.join(wins) or 'no measured row'))
-  lines.append('# fused median not below composed median at: ' + (', '.join(losses) or 'no measured row'))
-  print('\n'.join(lines[-2:]), flush=True)
-  out = pathlib.Path(args.out)
-  out.parent.mkdir(parents=True, exist_ok=True)
-  out.write_text('\n'.join(lines) + '\n')
+      paths = {f: pieces[f][piece] for f in (False, True)}
+      got = pathbench.measure(paths, args.calls, args.rounds)
+      ops = [None if args.no_profiler else pathbench.device_ops(paths[f]) for f in paths]
+      report.verdict(f'{name} {piece}', pathbench.median_below(got[True], got[False]))
+      report.add(row(name, piece, got[False], got[True], ops, moved))
+  report.closing()
+  report.write()
 
 
 if __name__ == '__main__':

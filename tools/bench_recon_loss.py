@@ -28,7 +28,6 @@ Needs a GPU: there is no CPU fallback and no figure without one.
 """
 import argparse
 import pathlib
-import statistics
 import sys
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
@@ -37,9 +36,9 @@ sys.path.insert(0, str(ROOT))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from tools.bench_twohot import device_ops, device_us  # noqa: E402
+from tools import pathbench  # noqa: E402
+from tools.pathbench import COPY_CEILING_GBS  # noqa: E402
 
-CEILING = 6290.0                                  # GB/s, the streaming-copy ceiling profiles/ records
 # (head, shape of x, dims, dtype of x)
 ROWS = [
     ('image', (1024, 64, 64, 3), 3, 'bf16'), ('image', (1024, 64, 64, 3), 3, 'f32'),
@@ -61,18 +60,14 @@ def main():
   assert torch.cuda.is_available(), 'bench_recon_loss needs a GPU'
   from embodied_amd import outs
 
-  lines = [
-      f'# tools/bench_recon_loss.py --calls {args.calls} --rounds {args.rounds}',
-      f'# {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), torch {torch.__version__}'
-      '; outs.ImageMSE (uint8 frames), outs.MSE(symlog), outs.Binary (uint8 labels)',
+  device = pathbench.device_line() + '; outs.ImageMSE (uint8 frames), outs.MSE(symlog), outs.Binary (uint8 labels)'
+  report = pathbench.Report('bench_recon_loss.py', args, device, [
       '# us: time between device events over back-to-back calls, per call: median of rounds [min .. max] (calls per round)',
       '# ops: device operations per call (torch.profiler window), composed / fused',
-      f'# GB/s: bytes the fused call must move / its median time; copy ceiling {CEILING:.0f} GB/s (read + write)',
+      f'# GB/s: bytes the fused call must move / its median time; copy ceiling {COPY_CEILING_GBS:.0f} GB/s (read + write)',
       f'# {"row":<30}{"piece":<10}{"composed us":<32}{"fused us":<32}{"ops":<16}fused GB/s',
-  ]
-  print('\n'.join(lines), flush=True)
+  ])
   gen = np.random.default_rng(0)
-  wins, losses = [], []
   for head, shape, dims, kind in ROWS:
     dtype = torch.float32 if kind == 'f32' else torch.bfloat16
     x = torch.from_numpy(gen.standard_normal(shape).astype(np.float32)).cuda().to(dtype).requires_grad_()
@@ -102,31 +97,15 @@ def main():
     assert torch.allclose(a, b, rtol=1e-2 if kind == 'bf16' else 1e-4), (head, shape, kind)
     name = f'{head} ' + 'x'.join(str(s) for s in shape) + f' {kind}'
     for piece in ('forward', 'fwd+bwd'):
-      timed = lambda path, calls: device_us(pieces[path][piece], calls)
-      calls, rounds = {}, {path: [] for path in PATHS}
-      for path in PATHS:                                             # warm-up of this shape; sizes the rounds
-        timed(path, 3)
-        estimate = timed(path, 5)
-        calls[path] = int(min(args.calls, max(5, 0.1e6 / estimate)))
-      for _ in range(args.rounds):
-        for path in PATHS:
-          rounds[path].append(timed(path, calls[path]))
-      ops = {p: None if args.no_profiler else device_ops(pieces[p][piece]) for p in PATHS}
-      median = {p: statistics.median(rounds[p]) for p in PATHS}
-      cell = lambda p: f'{median[p]:9.1f} [{min(rounds[p]):.1f} .. {max(rounds[p]):.1f}] ({calls[p]})'
-      opcount = ' / '.join('not measured' if ops[p] is None else f'{ops[p]:.1f}' for p in PATHS)
-      (wins if median['fused'] < median['composed'] else losses).append(f'{name} {piece}')
-      rate = moved[piece] / median['fused'] * 1e-3
-      line = (f'  {name:<30}{piece:<10}{cell("composed"):<32}{cell("fused"):<32}{opcount:<16}'
-              f'{rate:.0f} = {rate / CEILING:.2f} of the ceiling ({moved[piece] / 1e6:.1f} MB)')
-      lines.append(line)
-      print(line, flush=True)
-  lines.append('# fused median below composed median at: ' + (', '.join(wins) or 'no measured row'))
-  lines.append('# fused median not below composed median at: ' + (', '.join(losses) or 'no measured row'))
-  print('\n'.join(lines[-2:]), flush=True)
-  out = pathlib.Path(args.out)
-  out.parent.mkdir(parents=True, exist_ok=True)
-  out.write_text('\n'.join(lines) + '\n')
+      paths = {path: pieces[path][piece] for path in PATHS}
+      got = pathbench.measure(paths, args.calls, args.rounds)
+      opcount = ' / '.join(pathbench.count(None if args.no_profiler else pathbench.device_ops(paths[p])) for p in PATHS)
+      report.verdict(f'{name} {piece}', pathbench.median_below(got['fused'], got['composed']))
+      rate = moved[piece] / got['fused'].median * 1e-3
+      report.add(f'  {name:<30}{piece:<10}{got["composed"].cell:<32}{got["fused"].cell:<32}{opcount:<16}'
+                 f'{rate:.0f} = {rate / COPY_CEILING_GBS:.2f} of the ceiling ({moved[piece] / 1e6:.1f} MB)')
+  report.closing()
+  report.write()
 
 
 if __name__ == '__main__':

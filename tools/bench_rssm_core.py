@@ -30,7 +30,6 @@ Needs a GPU: there is no CPU fallback and no figure without one.
 """
 import argparse
 import pathlib
-import statistics
 import sys
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
@@ -38,7 +37,8 @@ sys.path.insert(0, str(ROOT))
 
 import torch  # noqa: E402
 
-from tools.bench_twohot import COPY_CEILING_GBS, device_ops, device_us  # noqa: E402
+from tools import pathbench  # noqa: E402
+from tools.pathbench import COPY_CEILING_GBS  # noqa: E402
 
 NORM_SHAPES = [(16, 1024), (1024, 1024), (16384, 1024), (16, 8192), (1024, 8192)]
 GATE_SHAPES = [(16, 8192, 8), (1024, 8192, 8), (4096, 8192, 8), (1024, 512, 8)]
@@ -54,42 +54,28 @@ def main():
   assert torch.cuda.is_available(), 'bench_rssm_core needs a GPU'
   from embodied_amd import nets
 
-  lines = [
-      f'# tools/bench_rssm_core.py --calls {args.calls} --rounds {args.rounds}',
-      f'# {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), torch {torch.__version__}'
-      '; nets.norm_act (rms, silu, scale with a gradient) and nets.gru_gate',
+  device = pathbench.device_line() + '; nets.norm_act (rms, silu, scale with a gradient) and nets.gru_gate'
+  report = pathbench.Report('bench_rssm_core.py', args, device, [
       '# shape: norm rows x units; gate rows x deter / blocks',
       '# us: time between device events over back-to-back calls, per call: median of rounds [min .. max] (calls per round)',
       '# ops: device operations per call (torch.profiler window), composed / fused',
       f'# GB/s: bytes the fused call must move / its median time; copy ceiling {COPY_CEILING_GBS:.0f} GB/s (read + write)',
       f'# {"shape":<40}{"piece":<10}{"composed us":<34}{"fused us":<34}{"ops composed / fused":<22}fused GB/s',
-  ]
-  print('\n'.join(lines), flush=True)
+  ])
   gen = torch.Generator(device='cuda').manual_seed(0)
-  wins, losses = [], []
 
   def measure(name, pieces, moved, baseline='composed'):
     for piece in ('forward', 'fwd+bwd'):
-      calls, rounds = {}, {False: [], True: []}
-      for fused in rounds:                             # warm-up of this shape; sizes the rounds
-        device_us(pieces[fused][piece], 3)
-        estimate = device_us(pieces[fused][piece], 5)
-        calls[fused] = int(min(args.calls, max(5, 0.1e6 / estimate)))
-      for _ in range(args.rounds):
-        for fused in rounds:
-          rounds[fused].append(device_us(pieces[fused][piece], calls[fused]))
-      ops = {f: None if args.no_profiler else device_ops(pieces[f][piece]) for f in rounds}
-      median = {f: statistics.median(rounds[f]) for f in rounds}
-      cell = lambda f: f'{median[f]:9.1f} [{min(rounds[f]):.1f} .. {max(rounds[f]):.1f}] ({calls[f]})'
-      count = lambda f: 'not measured' if ops[f] is None else f'{ops[f]:.1f}'
+      paths = {f: pieces[f][piece] for f in (False, True)}
+      got = pathbench.measure(paths, args.calls, args.rounds)
+      ops = {f: None if args.no_profiler else pathbench.device_ops(paths[f]) for f in paths}
       if baseline == 'composed':
-        (wins if median[True] < median[False] else losses).append(f'{name} {piece}')
-      rate = moved[piece] / median[True] / 1e3
+        report.verdict(f'{name} {piece}', pathbench.median_below(got[True], got[False]))
+      rate = moved[piece] / got[True].median / 1e3
       label = name if baseline == 'composed' else f'{name} vs {baseline}'
-      line = (f'  {label:<40}{piece:<10}{cell(False):<34}{cell(True):<34}{count(False) + " / " + count(True):<22}'
-              f'{rate:.0f} = {rate / COPY_CEILING_GBS:.2f} of the ceiling')
-      lines.append(line)
-      print(line, flush=True)
+      report.add(f'  {label:<40}{piece:<10}{got[False].cell:<34}{got[True].cell:<34}'
+                 f'{pathbench.count(ops[False]) + " / " + pathbench.count(ops[True]):<22}'
+                 f'{rate:.0f} = {rate / COPY_CEILING_GBS:.2f} of the ceiling')
 
   for rows, units in NORM_SHAPES:
     for kind, dtype in (('f32', torch.float32), ('bf16', torch.bfloat16)):
@@ -138,12 +124,8 @@ def main():
       assert torch.allclose(a.float(), b.float(), rtol=2e-5 if kind == 'f32' else 2.0 ** -5, atol=2e-5 if kind == 'f32' else 2.0 ** -6)
       measure(f'gate {rows}x{deter}/{blocks} {kind}', pieces, {'forward': 5 * size, 'fwd+bwd': 14 * size})
 
-  lines.append('# fused median below composed median at: ' + (', '.join(wins) or 'no measured row'))
-  lines.append('# fused median not below composed median at: ' + (', '.join(losses) or 'no measured row'))
-  print('\n'.join(lines[-2:]), flush=True)
-  out = pathlib.Path(args.out)
-  out.parent.mkdir(parents=True, exist_ok=True)
-  out.write_text('\n'.join(lines) + '\n')
+  report.closing()
+  report.write()
 
 
 if __name__ == '__main__':

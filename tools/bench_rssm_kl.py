@@ -35,7 +35,6 @@ Needs a GPU: there is no CPU fallback and no figure without one.
 """
 import argparse
 import pathlib
-import statistics
 import sys
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
@@ -44,7 +43,8 @@ sys.path.insert(0, str(ROOT))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from tools.bench_twohot import COPY_CEILING_GBS, device_ops, device_us  # noqa: E402
+from tools import pathbench  # noqa: E402
+from tools.pathbench import COPY_CEILING_GBS, device_us  # noqa: E402
 
 SHAPES = [(rows, stoch, classes, kind) for rows in (1024, 16384) for stoch, classes in ((32, 32), (32, 64), (32, 96))
           for kind in ('f32', 'bf16')]
@@ -130,24 +130,20 @@ def main():
   assert torch.cuda.is_available(), 'bench_rssm_kl needs a GPU'
   from embodied_amd import outs
 
-  device = f'# {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), torch {torch.__version__}'
+  device = pathbench.device_line()
   acc = accuracy(outs, [device])
   print('\n'.join(acc), flush=True)
   path = pathlib.Path(args.accuracy)
   path.parent.mkdir(parents=True, exist_ok=True)
   path.write_text('\n'.join(acc) + '\n')
 
-  lines = [
-      f'# tools/bench_rssm_kl.py --calls {args.calls} --rounds {args.rounds}',
-      device + f'; outs.rssm_kl, unimix {UNIMIX}, free_nats {FREE_NATS}',
+  report = pathbench.Report('bench_rssm_kl.py', args, device + f'; outs.rssm_kl, unimix {UNIMIX}, free_nats {FREE_NATS}', [
       '# us: time between device events over back-to-back calls, per call: median of rounds [min .. max] (calls per round)',
       '# ops: device operations per call (torch.profiler window); the kernel rows: the C entry point alone',
       f'# GB/s: bytes the kernel must move / median time; copy ceiling {COPY_CEILING_GBS:.0f} GB/s (read + write)',
       f'# {"shape":<22}{"piece":<12}{"composed us":<34}{"fused us":<34}{"ops composed / fused":<22}fused GB/s',
-  ]
-  print('\n'.join(lines), flush=True)
+  ])
   gen = np.random.default_rng(0)
-  wins, losses = [], []
   for rows, stoch, classes, kind in SHAPES:
     dtype = torch.float32 if kind == 'f32' else torch.bfloat16
     make = lambda: torch.from_numpy(gen.standard_normal((rows, stoch, classes)).astype(np.float32)).cuda().to(dtype)
@@ -176,42 +172,21 @@ def main():
       assert torch.allclose(x, y, rtol=tol, atol=1e-5), (rows, stoch, classes, kind, 'grad')
     name = f'{rows}x{stoch}x{classes} {kind}'
     for piece in ('forward', 'fwd+bwd'):
-      def timed(fused, calls):
-        return device_us(pieces[fused][piece], calls)
-      calls, rounds = {}, {False: [], True: []}
-      for fused in rounds:                             # warm-up of this shape; sizes the rounds
-        timed(fused, 3)
-        estimate = timed(fused, 5)
-        calls[fused] = int(min(args.calls, max(5, 0.1e6 / estimate)))
-      for _ in range(args.rounds):
-        for fused in rounds:
-          rounds[fused].append(timed(fused, calls[fused]))
-      ops = {f: None if args.no_profiler else device_ops(pieces[f][piece]) for f in rounds}
-      cell = lambda f: (f'{statistics.median(rounds[f]):9.1f} [{min(rounds[f]):.1f} .. {max(rounds[f]):.1f}] '
-                        f'({calls[f]})')
-      count = lambda f: 'not measured' if ops[f] is None else f'{ops[f]:.1f}'
-      (wins if statistics.median(rounds[True]) < statistics.median(rounds[False]) else losses).append(f'{name} {piece}')
-      line = (f'  {name:<22}{piece:<12}{cell(False):<34}{cell(True):<34}'
-              f'{count(False) + " / " + count(True):<22}-')
-      lines.append(line)
-      print(line, flush=True)
+      paths = {f: pieces[f][piece] for f in (False, True)}
+      got = pathbench.measure(paths, args.calls, args.rounds)
+      ops = {f: None if args.no_profiler else pathbench.device_ops(paths[f]) for f in paths}
+      report.verdict(f'{name} {piece}', pathbench.median_below(got[True], got[False]))
+      report.add(f'  {name:<22}{piece:<12}{got[False].cell:<34}{got[True].cell:<34}'
+                 f'{pathbench.count(ops[False]) + " / " + pathbench.count(ops[True]):<22}-')
     for piece, call, moved in zip(('fwd kernel', 'grad kernel'), kernel_calls(post, prior, g_dyn, g_rep),
                                   (2 * size, 4 * size)):
       device_us(call, 50)
-      values = [device_us(call, args.calls) for _ in range(args.rounds)]
-      median = statistics.median(values)
-      rate = moved / median / 1e3
-      line = (f'  {name:<22}{piece:<12}{"":<34}'
-              f'{f"{median:9.1f} [{min(values):.1f} .. {max(values):.1f}] ({args.calls})":<34}'
-              f'{"- / 1.0":<22}{rate:.0f} = {rate / COPY_CEILING_GBS:.2f} of the ceiling')
-      lines.append(line)
-      print(line, flush=True)
-  lines.append('# fused median below composed median at: ' + (', '.join(wins) or 'no measured shape'))
-  lines.append('# fused median not below composed median at: ' + (', '.join(losses) or 'no measured shape'))
-  print('\n'.join(lines[-2:]), flush=True)
-  out = pathlib.Path(args.out)
-  out.parent.mkdir(parents=True, exist_ok=True)
-  out.write_text('\n'.join(lines) + '\n')
+      alone = pathbench.run_rounds({piece: call}, args.calls, args.rounds)[piece]
+      rate = moved / alone.median / 1e3
+      report.add(f'  {name:<22}{piece:<12}{"":<34}{alone.cell:<34}'
+                 f'{"- / 1.0":<22}{rate:.0f} = {rate / COPY_CEILING_GBS:.2f} of the ceiling')
+  report.closing(none='no measured shape')
+  report.write()
 
 
 if __name__ == '__main__':

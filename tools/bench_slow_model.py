@@ -47,6 +47,9 @@ import sys
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
+from tools import pathbench  # noqa: E402
+from tools.pathbench import COPY_CEILING_GBS  # noqa: E402
+
 LIMIT = 300                                               # seconds per set, start-up included
 RATE = 0.02                                               # configs.yaml:110, slowvalue
 VALUE_SIZES = {'value1m': (512, 4, 64), 'value200m': (8192, 64, 1024), 'value400m': (12288, 96, 1536)}   # deter, classes, units
@@ -71,8 +74,6 @@ def measure(name, args):
   """One set, in this process: prints its rows and its `verdict` lines."""
   import torch
   from embodied_amd import optim
-  from tools.bench_optim import host_us
-  from tools.bench_twohot import COPY_CEILING_GBS, device_us
   assert torch.cuda.is_available(), 'bench_slow_model needs a GPU'
   shapes = shapes_of(name)
   count = sum(math.prod(s) for s in shapes)
@@ -100,24 +101,16 @@ def measure(name, args):
         calls[f'{title} attached'] = opt.step
       else:
         calls[f'{title} step+update'] = lambda opt=opt, slow=slow: (opt.step(), slow.update())
-  per_round, rounds, host = {}, {k: [] for k in calls}, {}
-  for k, call in calls.items():                           # warm-up; sizes the rounds
-    device_us(call, 2)
-    estimate = device_us(call, 3)
-    per_round[k] = int(min(args.calls, max(3, 0.1e6 / estimate)))
-  for _ in range(args.rounds):
-    for k, call in calls.items():
-      rounds[k].append(device_us(call, per_round[k]))
-  for k, call in calls.items():
-    host[k] = statistics.median(host_us(call, per_round[k]) for _ in range(3))
+  got = pathbench.measure(calls, args.calls, args.rounds, warmup=(2, 3), floor=3)
+  host = {k: statistics.median(pathbench.host_us(call, got[k].calls, sync=False) for _ in range(3))
+          for k, call in calls.items()}
   assert slows['fused'].table_uploads == 1
-  median = {k: statistics.median(v) for k, v in rounds.items()}
-  print(f'device: {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), '
-        f'torch {torch.__version__}')
+  median = {k: v.median for k, v in got.items()}
+  print('device: ' + pathbench.device_line()[2:])
   print(f'row:   {name}: {count} parameters in {len(shapes)} tensors, {slows["fused"]._plan["n_chunks"]} chunks of '
         f'{optim.CHUNK}')
   for k in calls:
-    print(f'row:     {k:<20}{median[k]:10.1f} us [{min(rounds[k]):.1f} .. {max(rounds[k]):.1f}] ({per_round[k]})'
+    print(f'row:     {k:<20}{pathbench.cell(got[k].values, got[k].calls, 10, " us")}'
           f'   host {host[k]:8.1f} us')
   for k, per in (('fused', 12), ('laprop attached', 40), ('adam attached', 40)):
     rate = per * count / median[k] / 1e3
@@ -140,14 +133,12 @@ def main():
   if args.child:
     measure(args.child, args)
     return
-  lines = [
-      f'# tools/bench_slow_model.py --calls {args.calls} --rounds {args.rounds}',
-      None,                                               # the device, from the first set
+  report = pathbench.Report('bench_slow_model.py', args, None, [      # the device: from the first set
       f'# SlowModel(rate={RATE:g}, every=1); LaProp() and Adam() at their defaults, float32 gradients',
       '# us: time between device events over back-to-back calls, per call: median of rounds [min .. max] (calls per round)',
       '# host us: wall time up to the last enqueue, per call',
       '# lerp: torch._foreach_lerp_(dst, src, rate) at the same commit, on tensors of its own; another expression',
-  ]
+  ])
   verdicts = []
   for name in args.sets.split(','):
     command = [sys.executable, str(pathlib.Path(__file__).resolve()), '--child', name, '--calls', str(args.calls),
@@ -160,25 +151,19 @@ def main():
       sys.stderr.write(done.stderr[-4000:])
       sys.exit(f'bench_slow_model: {name} failed with status {done.returncode}; stopping, nothing written')
     for line in done.stdout.splitlines():
-      if line.startswith('device: ') and lines[1] is None:
-        lines[1] = '# ' + line[len('device: '):]
+      if line.startswith('device: ') and report.lines[1] is None:
+        report.lines[1] = '# ' + line[len('device: '):]
       elif line.startswith('row: '):
-        lines.append(line[len('row: '):])
-        print(lines[-1], flush=True)
+        report.add(line[len('row: '):])
       elif line.startswith('verdict: '):
         verdicts.append(line[len('verdict: '):].split('|'))
   for what, title in (('composed', 'update() median below the composed median'),
                       ('lerp', 'update() median below the _foreach_lerp_ median'),
                       ('laprop', 'LaProp attached step median below step() + update()'),
                       ('adam', 'Adam attached step median below step() + update()')):
-    wins = [v[0] for v in verdicts if v[1] == what and v[2] == 'below']
-    losses = [v[0] for v in verdicts if v[1] == what and v[2] == 'not below']
-    lines.append(f'# {title} at: ' + (', '.join(wins) or 'no measured row'))
-    lines.append(f'# not at: ' + (', '.join(losses) or 'no measured row'))
-  print('\n'.join(lines[-8:]), flush=True)
-  out = pathlib.Path(args.out)
-  out.parent.mkdir(parents=True, exist_ok=True)
-  out.write_text('\n'.join(line for line in lines if line is not None) + '\n')
+    report.closing(f'{title} at', 'not at', wins=[v[0] for v in verdicts if v[1] == what and v[2] == 'below'],
+                   losses=[v[0] for v in verdicts if v[1] == what and v[2] == 'not below'])
+  report.write()
 
 
 if __name__ == '__main__':

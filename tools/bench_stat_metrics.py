@@ -38,8 +38,7 @@ sys.path.insert(0, str(ROOT))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from tools.bench_normal_policy import enqueue_us  # noqa: E402
-from tools.bench_twohot import device_ops, device_us  # noqa: E402
+from tools import pathbench  # noqa: E402
 
 IMAG_SHAPES = [(16, 16), (1024, 16), (1024, 17), (4096, 16)]
 LOSS_SHAPES = [(10, 16, 64), (10, 64, 64)]
@@ -96,47 +95,30 @@ def main():
   parser.add_argument('--no-profiler', action='store_true')
   args = parser.parse_args()
   assert torch.cuda.is_available(), 'bench_stat_metrics needs a GPU'
-  lines = [
-      f'# tools/bench_stat_metrics.py --calls {args.calls} --rounds {args.rounds}',
-      f'# {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), torch {torch.__version__}'
-      '; scans.imag_metrics (two action keys with limits, perc retnorm, float vstats) and outs.total_loss',
+  device = (pathbench.device_line()
+            + '; scans.imag_metrics (two action keys with limits, perc retnorm, float vstats) and outs.total_loss')
+  report = pathbench.Report('bench_stat_metrics.py', args, device, [
       '# us: time between device events over back-to-back calls, per call: median of rounds [min .. max] (calls per round)',
       '# enqueue: host time per fused call without waiting for the device; `host`: the fused us is the enqueue time',
       '# ops: device operations per call (torch.profiler window), composed / fused',
       f'# {"call":<28}{"piece":<10}{"composed us":<34}{"fused us":<34}{"enqueue us":<14}ops composed / fused',
-  ]
-  print('\n'.join(lines), flush=True)
+  ])
   gen = np.random.default_rng(0)
   jobs = [(f'imag_metrics {n}x{t}', imag_pieces(n, t, gen)) for n, t in IMAG_SHAPES]
   jobs += [(f'total_loss K={k} {b}x{t}', loss_pieces(k, b, t, gen)) for k, b, t in LOSS_SHAPES]
-  wins, losses = [], []
   for name, pieces in jobs:
     for piece, paths in pieces.items():
-      calls, rounds, issue = {}, {False: [], True: []}, []
-      for fused in rounds:                             # warm-up of this shape; sizes the rounds
-        device_us(paths[fused], 3)
-        estimate = device_us(paths[fused], 5)
-        calls[fused] = int(min(args.calls, max(5, 0.1e6 / estimate)))
-      for _ in range(args.rounds):
-        for fused in rounds:
-          rounds[fused].append(device_us(paths[fused], calls[fused]))
-        issue.append(enqueue_us(paths[True], calls[True]))
-      ops = {f: None if args.no_profiler else device_ops(paths[f]) for f in rounds}
-      median = {f: statistics.median(rounds[f]) for f in rounds}
-      enqueue = statistics.median(issue)
-      cell = lambda f: f'{median[f]:9.1f} [{min(rounds[f]):.1f} .. {max(rounds[f]):.1f}] ({calls[f]})'
-      number = lambda f: 'not measured' if ops[f] is None else f'{ops[f]:.1f}'
-      (wins if median[True] < median[False] else losses).append(f'{name} {piece}')
-      bound = f'{enqueue:.1f}' + (' host' if median[True] <= 1.15 * enqueue else '')
-      line = f'  {name:<28}{piece:<10}{cell(False):<34}{cell(True):<34}{bound:<14}{number(False)} / {number(True)}'
-      lines.append(line)
-      print(line, flush=True)
-  lines.append('# fused median below composed median at: ' + (', '.join(wins) or 'no measured row'))
-  lines.append('# fused median not below composed median at: ' + (', '.join(losses) or 'no measured row'))
-  print('\n'.join(lines[-2:]), flush=True)
-  out = pathlib.Path(args.out)
-  out.parent.mkdir(parents=True, exist_ok=True)
-  out.write_text('\n'.join(lines) + '\n')
+      issue = []
+      enqueue = lambda calls: issue.append(pathbench.host_us(paths[True], calls[True], sync=False))
+      got = pathbench.measure(paths, args.calls, args.rounds, after_round=enqueue)
+      ops = {f: None if args.no_profiler else pathbench.device_ops(paths[f]) for f in paths}
+      report.verdict(f'{name} {piece}', pathbench.median_below(got[True], got[False]))
+      enqueued = statistics.median(issue)
+      bound = f'{enqueued:.1f}' + (' host' if got[True].median <= 1.15 * enqueued else '')
+      report.add(f'  {name:<28}{piece:<10}{got[False].cell:<34}{got[True].cell:<34}{bound:<14}'
+                 f'{pathbench.count(ops[False])} / {pathbench.count(ops[True])}')
+  report.closing()
+  report.write()
 
 
 if __name__ == '__main__':

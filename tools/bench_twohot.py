@@ -34,7 +34,6 @@ Needs a GPU: there is no CPU fallback and no figure without one.
 """
 import argparse
 import pathlib
-import statistics
 import sys
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
@@ -43,20 +42,11 @@ sys.path.insert(0, str(ROOT))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from tools import pathbench  # noqa: E402
+from tools.pathbench import COPY_CEILING_GBS, device_us  # noqa: E402
+
 SHAPES = [(16384, 255, 'f32'), (16384, 255, 'bf16'), (1024, 255, 'f32'), (1008, 255, 'f32'), (16384, 256, 'f32')]
 COEFS = (1.0, 0.7)
-COPY_CEILING_GBS = 6290.0       # the copy ceiling of this part, read + write bytes
-
-
-def device_us(call, calls):
-  start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  torch.cuda.synchronize()
-  start.record()
-  for _ in range(calls):
-    call()
-  stop.record()
-  torch.cuda.synchronize()
-  return start.elapsed_time(stop) * 1e3 / calls
 
 
 def backward_call(forward, logits, gout):
@@ -89,22 +79,6 @@ def kernel_calls(outs, logits, bins, targets, gout):
   return stats, grads
 
 
-def device_ops(call, calls=3):
-  """Device-side events per call as torch.profiler sees them (None: no profiler)."""
-  try:
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-      for _ in range(calls):
-        call()
-      torch.cuda.synchronize()
-    events = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
-    return len(events) / calls
-  except Exception as e:      # a figure that was not measured is reported as such
-    print(f'# torch.profiler window failed: {e!r}', file=sys.stderr)
-    return None
-
-
 def main():
   parser = argparse.ArgumentParser()
   parser.add_argument('--calls', type=int, default=1000)
@@ -115,17 +89,14 @@ def main():
   assert torch.cuda.is_available(), 'bench_twohot needs a GPU'
   from embodied_amd import outs
 
-  lines = [
-      f'# tools/bench_twohot.py --calls {args.calls} --rounds {args.rounds}',
-      f'# {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), torch {torch.__version__}; outs.TwoHot, two targets, coefs {COEFS}',
+  device = pathbench.device_line() + f'; outs.TwoHot, two targets, coefs {COEFS}'
+  report = pathbench.Report('bench_twohot.py', args, device, [
       '# us: time between device events over back-to-back calls, per call: median of rounds [min .. max] (calls per round)',
       '# ops: device operations per call (torch.profiler window); the kernel rows: the C entry point alone',
       f'# GB/s: bytes the kernel must move / median time; copy ceiling {COPY_CEILING_GBS:.0f} GB/s (read + write)',
       f'# {"shape":<18}{"piece":<10}{"composed us":<34}{"fused us":<34}{"ops composed / fused":<22}fused GB/s',
-  ]
-  print('\n'.join(lines), flush=True)
+  ])
   gen = np.random.default_rng(0)
-  wins, losses = [], []
   for rows, n, kind in SHAPES:
     dtype = torch.float32 if kind == 'f32' else torch.bfloat16
     bins = outs.symexp_twohot_bins(n)
@@ -154,47 +125,23 @@ def main():
     for f in (False, True):
       pieces[f]['backward'] = backward_call(pieces[f]['forward'], logits, gout)
     for piece in ('stats', 'loss_sum', 'backward'):
-      def timed(fused, calls):
-        return device_us(pieces[fused][piece], calls)
-      calls, rounds = {}, {False: [], True: []}
-      for fused in rounds:                             # warm-up of this shape; sizes the rounds
-        timed(fused, 3)
-        estimate = timed(fused, 5)
-        calls[fused] = int(min(args.calls, max(5, 0.2e6 / estimate)))
-      for _ in range(args.rounds):
-        for fused in rounds:
-          rounds[fused].append(timed(fused, calls[fused]))
-      ops = {f: None if args.no_profiler else device_ops(pieces[f][piece]) for f in rounds}
-      cell = lambda f: (f'{statistics.median(rounds[f]):9.1f} [{min(rounds[f]):.1f} .. {max(rounds[f]):.1f}] '
-                        f'({calls[f]})')
-      count = lambda f: 'not measured' if ops[f] is None else f'{ops[f]:.1f}'
+      paths = {f: pieces[f][piece] for f in (False, True)}
+      got = pathbench.measure(paths, args.calls, args.rounds, budget_us=0.2e6)
+      ops = {f: None if args.no_profiler else pathbench.device_ops(paths[f]) for f in paths}
       name = f'{rows}x{n} {kind}'
-      if max(rounds[True]) < min(rounds[False]):
-        wins.append(f'{name} {piece}')
-      else:
-        losses.append(f'{name} {piece}')
-      line = (f'  {name:<18}{piece:<10}{cell(False):<34}{cell(True):<34}'
-              f'{count(False) + " / " + count(True):<22}-')
-      lines.append(line)
-      print(line, flush=True)
+      report.verdict(f'{name} {piece}', pathbench.every_round_below(got[True], got[False]))
+      report.add(f'  {name:<18}{piece:<10}{got[False].cell:<34}{got[True].cell:<34}'
+                 f'{pathbench.count(ops[False]) + " / " + pathbench.count(ops[True]):<22}-')
     for piece, call, moved in zip(('stats kernel', 'grad kernel'), kernel_calls(outs, logits, bins, targets, gout),
                                   (size, 2 * size)):
       device_us(call, 50)
-      values = [device_us(call, args.calls) for _ in range(args.rounds)]
-      median = statistics.median(values)
-      rate = moved / median / 1e3
-      line = (f'  {f"{rows}x{n} {kind}":<18}{piece:<14}{"":<30}'
-              f'{f"{median:9.1f} [{min(values):.1f} .. {max(values):.1f}] ({args.calls})":<34}'
-              f'{"- / 1.0":<22}{rate:.0f} = {rate / COPY_CEILING_GBS:.2f} of the ceiling')
-      lines.append(line)
-      print(line, flush=True)
-  lines.append('# fused beats composed, every round of one below every round of the other, at: '
-               + (', '.join(wins) or 'no measured shape'))
-  lines.append('# fused does not beat composed in every round at: ' + (', '.join(losses) or 'no measured shape'))
-  print('\n'.join(lines[-2:]), flush=True)
-  out = pathlib.Path(args.out)
-  out.parent.mkdir(parents=True, exist_ok=True)
-  out.write_text('\n'.join(lines) + '\n')
+      alone = pathbench.run_rounds({piece: call}, args.calls, args.rounds)[piece]
+      rate = moved / alone.median / 1e3
+      report.add(f'  {f"{rows}x{n} {kind}":<18}{piece:<14}{"":<30}{alone.cell:<34}'
+                 f'{"- / 1.0":<22}{rate:.0f} = {rate / COPY_CEILING_GBS:.2f} of the ceiling')
+  report.closing('fused beats composed, every round of one below every round of the other, at',
+                 'fused does not beat composed in every round at', none='no measured shape')
+  report.write()
 
 
 if __name__ == '__main__':
