@@ -29,6 +29,8 @@ EMB_RECON_MSE, EMB_RECON_MSE_SYMLOG, EMB_RECON_SIGMOID_MSE, EMB_RECON_BINARY = 0
 NORMAL_BOUNDED, NORMAL_LOGSTD = 0, 1
 STAT_NONE, STAT_MUL_ADD, STAT_SUB_DIV = 0, 1, 2
 STAT_MAX_ENTRIES, STAT_VALUES = 48, 6      # EMB_STAT_MAX_ENTRIES, EMB_STAT_VALUES
+DICT_ONEHOT, DICT_NONE, DICT_SYMLOG = 0, 1, 2
+DICT_MAX_KEYS = 16                         # EMB_DICT_MAX_KEYS
 
 
 class EmbError(RuntimeError):
@@ -110,6 +112,12 @@ class StatEntry(C.Structure):
 class FillEntry(C.Structure):
   """emb_fill_entry_t: one gradient buffer of emb_mean_fill."""
   _fields_ = [('out', C.c_void_p), ('n', C.c_int64), ('scale', C.c_float), ('reserved', C.c_int32)]
+
+
+class DictEntry(C.Structure):
+  """emb_dict_entry_t: one key of emb_dict_concat."""
+  _fields_ = [('x', C.c_void_p), ('dtype', C.c_int32), ('kind', C.c_int32), ('elements', C.c_int32),
+              ('classes', C.c_int32), ('first', C.c_int32), ('reserved', C.c_int32)]
 
 
 class SelectorCallbacks(C.Structure):
@@ -287,6 +295,8 @@ SIGNATURES = {
     'emb_stat_rows': [p, i64, p, p, p],
     'emb_mean_fill': [p, i64, p, p],
     'emb_stat_rows_launches': [p],
+    'emb_dict_concat': [p, i64, i64, i64, p, i64, i32, p, i32, p],
+    'emb_dict_concat_launches': [p],
     'emb_synth_env_step': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p],
     'emb_synth_env_step_masked': [p, p, p, p, p, i64, i64, i64, i64, p, p, i32, p, p, i64, i32, p],
     'emb_env_mask_supported': [i64, i32],
@@ -429,7 +439,7 @@ class _FastApi:
       'emb_copy_bytes': 'ints', 'emb_mask_actions_notify': 'ints', 'emb_normalize': 'ints',
       'emb_ppo_targets': 'ppo_targets',
       'emb_scan_lambda_cont': 'scan_cont', 'emb_dreamer_targets': 'dreamer_targets',
-      'emb_stat_rows': 'ints', 'emb_mean_fill': 'ints',
+      'emb_stat_rows': 'ints', 'emb_mean_fill': 'ints', 'emb_dict_concat': 'ints',
   }
 
   def __init__(self, module):

@@ -24,6 +24,7 @@ SOURCES = ['movers.hip', 'step.hip', 'scans.hip', 'synth_env.hip', 'direct_comm.
            'conv_stage.hip', 'conv_stage_abi.cpp',
            'onehot_sample_abi.cpp', 'recon_loss.hip', 'recon_loss_abi.cpp', 'normal_policy.hip',
            'normal_policy_abi.cpp', 'block_linear_abi.cpp', 'stat_rows.hip', 'stat_rows_abi.cpp',
+           'dict_concat.hip', 'dict_concat_abi.cpp',
            'replay_abi.cpp', 'index_abi.cpp', 'kernels_abi.cpp', 'env_abi.cpp', 'comm_abi.cpp', 'normalize_abi.cpp',
            'ppo_targets_abi.cpp', 'dreamer_targets_abi.cpp', 'twohot_abi.cpp', 'onehot_kl_abi.cpp',
            'policy_loss_abi.cpp', 'optim_abi.cpp']

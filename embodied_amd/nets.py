@@ -568,3 +568,273 @@ def gru_gate(x, deter, blocks, fused=None):
   if _gate_path(fused, rows, width, blocks) and rows > 0:
     return _FusedGate.apply(x, deter, blocks)
   return _composed_gru_gate(x, deter, blocks)
+
+
+# ------------------------------------------------------------- DictConcat --
+# csrc/dict_concat.h: at most 16 keys (a row's availability flags are one 16-bit
+# word), a row of at most 16 384 columns, classes at most 16 384, 32-bit indices
+# into `out`.  Structural limits.  Whether `fused=None` takes the kernel inside
+# them is `_dict_path`'s answer, with the measured figures beside it.
+DICT_MAX_KEYS = _lib.DICT_MAX_KEYS
+DICT_MAX_WIDTH = 16384
+DICT_MAX_CLASSES = 16384
+DICT_MAX_ELEMENTS = 2 ** 31 - 1
+SQUISHES = {None: _lib.DICT_NONE, 'none': _lib.DICT_NONE, 'symlog': _lib.DICT_SYMLOG}
+_DICT_DTYPES = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.int32: _lib.I32, torch.int64: _lib.I64,
+                torch.uint8: _lib.U8, torch.bool: _lib.BOOL}
+_DICT_FLOATS = (torch.float32, torch.bfloat16)
+
+
+def dict_concat_launches():
+  """Kernel launches `emb_dict_concat` has issued in this process."""
+  return _lib.launches('dict_concat')
+
+
+def _dict_path(fused, fits):
+  """True: the kernel, False: the composed path (`DictConcat` says when).  `fits`
+  is what the kernel takes, as `_fused_path` reads it.  The kernel's median was
+  below the composed path's at all 18 rows of profiles/dict_concat_bench.txt --
+  two discrete and two float keys at 16 rows: 16.6 us against 194.2; 16 mixed keys
+  at 1024 rows: 39.1 / 964.5; the Encoder's 8 symlog keys of 1024 columns at 65 536
+  rows: f32 675.7 / 1240.8, bf16 938.3 / 1224.9 -- so `fused=None` takes it wherever
+  it fits and no size constant sits here."""
+  if all(holds for holds, _ in fits):
+    return fused is None or bool(fused)
+  return _fused_path('dict_concat', fused, *fits)
+
+
+def _available(x, bdims):
+  """nets.py:80-99 with `bdims`, for one tensor."""
+  if x.dtype.is_floating_point:
+    mask = x != -np.inf
+  elif x.dtype in (torch.int8, torch.int16, torch.int32, torch.int64):
+    mask = x != -1
+  elif x.dtype in (torch.uint8, torch.bool):
+    return torch.ones(x.shape[:bdims], dtype=torch.bool, device=x.device)
+  else:
+    raise NotImplementedError(x.dtype)
+  return mask.flatten(bdims).all(-1) if mask.dim() > bdims else mask
+
+
+def _where(condition, x, y):
+  """nets.py:67-73 for one tensor: the condition's trailing axes are added."""
+  assert condition.dtype == torch.bool, condition.dtype
+  return torch.where(condition.reshape(*condition.shape, *([1] * (x.dim() - condition.dim()))), x, y)
+
+
+def _mask(x, mask):
+  """nets.py:76-77."""
+  return _where(mask, x, torch.zeros_like(x))
+
+
+def _symlog(x):
+  """nets.py:59-60."""
+  return torch.sign(x) * torch.log1p(torch.abs(x))
+
+
+def _composed_dict_concat(xs, keys, spaces, classes, fdims, squish, dtype, reset, unit):
+  """nets.py:476-500 operation by operation, then rssm.py:76-79 and rssm.py:137.
+  `jax.nn.one_hot` is its definition, a comparison against arange(classes): an
+  index outside [0, classes) gives zeros (torch's own one_hot refuses one)."""
+  bdims = xs[keys[0]].dim() - len(spaces[keys[0]].shape)
+  ys = []
+  for key in keys:
+    x = xs[key]
+    m = _available(x, bdims)
+    x = _mask(x, m)
+    if spaces[key].discrete:
+      x = x.to(torch.int32)
+      x = (x.unsqueeze(-1) == torch.arange(classes[key], dtype=torch.int32, device=x.device)).to(dtype)
+    else:
+      if squish == 'symlog':
+        x = _symlog(x)
+      x = x.to(dtype)
+    x = _mask(x, m)
+    ys.append(x.reshape(*x.shape[:bdims + fdims - 1], int(np.prod(x.shape[bdims + fdims - 1:], dtype=np.int64))))
+  y = torch.cat(ys, -1)
+  if reset is not None:                            # rssm.py:76-79: both masks are this one
+    y = _mask(y, ~reset.to(torch.bool))
+  if unit:                                         # rssm.py:137, in the compute dtype
+    y = y / torch.maximum(torch.ones((), dtype=y.dtype, device=y.device), torch.abs(y))
+  return y
+
+
+class DictConcat:
+  """`nn.DictConcat(spaces, fdims, squish)` (embodied/jax/nets.py:467-500): a dict
+  of CUDA tensors, one per key of `spaces` in sorted order, as one `(*batch, width)`
+  tensor of `dtype` (float32 or bfloat16, the reference's COMPUTE_DTYPE).  A
+  discrete space becomes the one-hot of its `classes` per element, any other the
+  `squish` (None or 'symlog') of its values; a row of a key with an element that is
+  not available (nets.py:80-99: -inf in a float, -1 in a signed integer) is zeros
+  in that key's columns.  The batch axes are those of the first key in front of
+  its space's shape (nets.py:478).
+
+      concat = nets.DictConcat(act_space)
+      action = concat(prevact, reset=reset, unit=True)       # rssm.py:76-79, 137
+      vector = nets.DictConcat(vspace, squish='symlog')(obs)  # rssm.py:216-220
+
+  `reset` (`(*batch,)`, bool or uint8): rows where it is set are zeros, which is
+  both masks of rssm.py:76-79.  `unit=True` stores every continuous value v as
+  v / max(1, |v|) (rssm.py:137).  `out`: a tensor `(*batch, width)` of `dtype` to
+  write into, or a column slice of one (unit column stride, batch axes that
+  collapse into one row stride); it is returned.  The result never requires grad:
+  the reference's three uses feed data or stop-gradient actions.
+
+  Two paths.  Composed restates the reference operation by operation in torch
+  (the definition, every size, CPU tensors excepted: there is no CPU fallback).
+  Fused is `emb_dict_concat`: ONE launch for inputs of float32, bfloat16, int32,
+  int64, uint8 or bool, at most 16 keys, 16 384 columns and 16 384 classes,
+  `fdims=1`; float32 arithmetic rounded once at the store, no atomics, the same
+  bits run to run.  `fused=None` takes the kernel where it fits, True / False
+  force a path (True raises where it does not fit, and says why).  An input that
+  requires grad does not fit.  No rows: the composed path, nothing is launched.
+
+  The documented differences.  An int64 index beyond the int32 range is out of
+  range on the kernel (zeros); composed wraps it, as `astype(int32)` would -- the
+  reference never sees one, JAX runs without x64.  `symlog` of a bfloat16 input is
+  float32 arithmetic on the kernel and bfloat16 arithmetic composed.  With `unit`
+  the kernel divides before it rounds and the reference after: for every finite v
+  the bits are the same (|v| <= 1 stores the rounded v, anything else +-1).
+
+  The key table is built once per (shapes, dtypes) of a call and kept; a call
+  only writes the addresses into it."""
+
+  def __init__(self, spaces, fdims=1, squish=None, dtype=torch.bfloat16):
+    if int(fdims) < 1:
+      raise ValueError(f'DictConcat: fdims = {fdims}, needs at least 1 (nets.py:470)')
+    if squish not in SQUISHES:
+      raise ValueError(f'DictConcat: squish = {squish!r}, needs None or \'symlog\'')
+    if dtype not in _DTYPES:
+      raise TypeError(f'DictConcat: dtype must be float32 or bfloat16, got {dtype}')
+    if not spaces:
+      raise ValueError('DictConcat: no spaces')
+    self.keys = sorted(spaces.keys())
+    self.spaces, self.fdims, self.dtype = dict(spaces), int(fdims), dtype
+    self.squish = None if squish in (None, 'none') else squish
+    self.classes, self.spans = {}, {}
+    for key in self.keys:
+      space = self.spaces[key]
+      if space.dtype == np.uint8 and len(space.shape) in (2, 3):
+        raise NotImplementedError('Images are not supported.')
+      elements = int(np.prod(space.shape, dtype=np.int64))
+      if space.discrete:
+        classes = np.asarray(space.classes).flatten()
+        if classes.size and not (classes == classes[0]).all():
+          raise ValueError(f'DictConcat: the elements of {key!r} differ in classes: {classes.tolist()} (nets.py:490)')
+        self.classes[key] = int(classes[0]) if classes.size else 0
+        self.spans[key] = elements * self.classes[key]
+      else:
+        self.spans[key] = elements
+    self.width = sum(self.spans.values())
+    self._tables = {}
+
+  def _table(self, signature):
+    """The ctypes key table of inputs with this (dtype per key): everything but the addresses."""
+    table = self._tables.get(signature)
+    if table is None:
+      table = (_lib.DictEntry * len(self.keys))()
+      first = 0
+      for entry, key, dtype in zip(table, self.keys, signature):
+        space = self.spaces[key]
+        entry.dtype = _DICT_DTYPES[dtype]
+        entry.kind = _lib.DICT_ONEHOT if space.discrete else SQUISHES[self.squish]
+        entry.elements = int(np.prod(space.shape, dtype=np.int64))
+        entry.classes = self.classes.get(key, 0)
+        entry.first = first
+        first += self.spans[key]
+      self._tables[signature] = table
+    return table
+
+  def _fits(self, xs, rows, stride):
+    """What the kernel takes, as (holds, wording) in the order it is checked."""
+    fits = [
+        (self.fdims == 1, f'fdims = {self.fdims}, the kernel writes one feature axis'),
+        (len(self.keys) <= DICT_MAX_KEYS, f'{len(self.keys)} keys, the kernel takes at most {DICT_MAX_KEYS}'),
+        (1 <= self.width <= DICT_MAX_WIDTH, f'{self.width} columns, the kernel writes a row of 1 .. {DICT_MAX_WIDTH}'),
+        (max(self.classes.values(), default=1) <= DICT_MAX_CLASSES and min(self.classes.values(), default=1) >= 1,
+         f'classes of {sorted(self.classes.values())}, the kernel takes 1 .. {DICT_MAX_CLASSES}'),
+        (rows * max(stride, 1) <= DICT_MAX_ELEMENTS, f'{rows} rows {stride} elements apart, the kernel indexes at most 2^31 - 1'),
+        (not any(xs[k].requires_grad for k in self.keys), 'an input requires grad, the kernel has no backward'),
+    ]
+    for key in self.keys:
+      dtype, space = xs[key].dtype, self.spaces[key]
+      fits.append((dtype in _DICT_DTYPES, f'{key!r} is {dtype}, the kernel reads float32, bfloat16, int32, int64, uint8 and bool'))
+      fits.append((not (space.discrete and dtype in _DICT_FLOATS), f'{key!r} is a discrete space fed {dtype}, the kernel compares integers'))
+      fits.append((not (self.squish and not space.discrete and dtype not in _DICT_FLOATS),
+                   f'{key!r} is {dtype} under {self.squish}, the kernel squishes floats'))
+    return fits
+
+  def __call__(self, xs, reset=None, unit=False, out=None, fused=None):
+    keys = self.keys
+    missing = [k for k in keys if k not in xs]
+    if missing:
+      raise KeyError(f'DictConcat: no input for {missing} (nets.py:477)')
+    for key in keys:
+      _check_device('DictConcat', xs[key])
+    first = xs[keys[0]]
+    bdims = first.dim() - len(self.spaces[keys[0]].shape)
+    if bdims < 0:
+      raise ValueError(f'DictConcat: {keys[0]!r} of shape {tuple(first.shape)}, its space is {self.spaces[keys[0]].shape}')
+    batch = tuple(first.shape[:bdims])
+    for key in keys:
+      if tuple(xs[key].shape[bdims:]) != tuple(self.spaces[key].shape) or tuple(xs[key].shape[:bdims]) != batch:
+        raise ValueError(f'DictConcat: {key!r} of shape {tuple(xs[key].shape)}, batch {batch} and its space '
+                         f'{tuple(self.spaces[key].shape)} need {(*batch, *self.spaces[key].shape)} (nets.py:485)')
+      if xs[key].device != first.device:
+        raise ValueError(f'DictConcat: {key!r} on {xs[key].device}, {keys[0]!r} on {first.device}')
+    rows = int(np.prod(batch, dtype=np.int64))
+    if reset is not None:
+      _check_device('DictConcat', reset)
+      if reset.dtype not in (torch.bool, torch.uint8) or tuple(reset.shape) != batch:
+        raise ValueError(f'DictConcat: reset of {reset.dtype} {tuple(reset.shape)}, needs bool or uint8 {batch}')
+    stride = self.width
+    if out is not None:
+      _check_device('DictConcat', out)
+      stride = self._out_stride(out, batch)
+    if _dict_path(fused, self._fits(xs, rows, stride)) and rows > 0:
+      return self._fused(xs, batch, rows, reset, unit, out, stride)
+    with torch.no_grad():
+      y = _composed_dict_concat(xs, keys, self.spaces, self.classes, self.fdims, self.squish, self.dtype, reset, unit)
+    if out is None:
+      return y
+    out.copy_(y)
+    return out
+
+  def _out_stride(self, out, batch):
+    """Elements from one row of `out` to the next; refuses what is no (rows, width) view."""
+    if out.dtype != self.dtype or tuple(out.shape) != (*batch, self.width) or self.fdims != 1:
+      raise ValueError(f'DictConcat: out of {out.dtype} {tuple(out.shape)}, needs {self.dtype} {(*batch, self.width)}')
+    if out.requires_grad:
+      raise ValueError('DictConcat: out requires grad')
+    strides, shape = out.stride(), out.shape
+    if self.width > 1 and strides[-1] != 1:
+      raise ValueError(f'DictConcat: out has a column stride of {strides[-1]}, needs 1')
+    live = [i for i in range(len(batch)) if shape[i] > 1]
+    if not live:
+      return self.width
+    for i, j in zip(live[:-1], live[1:]):
+      if strides[i] != strides[j] * shape[j]:
+        raise ValueError(f'DictConcat: the batch axes of out (strides {strides}) do not collapse into one row stride')
+    if strides[live[-1]] < self.width:
+      raise ValueError(f'DictConcat: the rows of out are {strides[live[-1]]} elements apart, fewer than {self.width}')
+    return strides[live[-1]]
+
+  def _fused(self, xs, batch, rows, reset, unit, out, stride):
+    held = [xs[k].detach().contiguous() for k in self.keys]          # alive until the launch is enqueued
+    table = self._table(tuple(x.dtype for x in held))
+    for entry, x in zip(table, held):
+      entry.x = x.data_ptr()
+    device = held[0].device
+    if out is None:
+      out = _lib.empty((*batch, self.width), self.dtype, device)
+    if reset is not None:
+      reset = reset.contiguous()
+    _lib.fast.emb_dict_concat(table, len(held), rows, self.width, out.data_ptr(), stride, _DTYPES[self.dtype],
+                              _address(reset), int(bool(unit)), _lib.raw_stream(device))
+    return out
+
+
+def dict_concat(xs, spaces, fdims=1, squish=None, dtype=torch.bfloat16, reset=None, unit=False, out=None, fused=None):
+  """`DictConcat(spaces, fdims, squish, dtype)(xs, reset, unit, out, fused)` as a
+  function; the key table is built on every call."""
+  return DictConcat(spaces, fdims, squish, dtype)(xs, reset=reset, unit=unit, out=out, fused=fused)

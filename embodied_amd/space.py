@@ -55,6 +55,17 @@ class Space:
     return self._discrete
 
   @property
+  def classes(self):
+    # elements.Space.classes, as nn.DictConcat reads it (embodied/jax/nets.py:489):
+    # high is exclusive, as in `sample`; a bool space has two.
+    assert self._discrete, self
+    if self._dtype == bool:
+      classes = np.full(self._shape, 2, np.int64)
+    else:
+      classes = self._high.astype(np.int64) - self._low.astype(np.int64)
+    return int(classes.item()) if not classes.ndim else classes
+
+  @property
   def nbytes(self):
     return int(np.prod(self._shape, dtype=np.int64)) * self._dtype.itemsize
 

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports (167 functions). */
+ * it exports (169 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -56,7 +56,7 @@ extern "C" {
  * emb_optim_grad_norms, emb_optim_adam_update, emb_slow_table, emb_slow_update,
  * emb_optim_update_slow, emb_optim_adam_update_slow, emb_pool_norm_act,
  * emb_pool_norm_act_grad, emb_norm_act_upsample, emb_norm_act_upsample_grad,
- * emb_conv_stage_launches
+ * emb_conv_stage_launches, emb_dict_concat, emb_dict_concat_launches
  * (additions only).                                                         */
 #define EMB_ABI_VERSION 5
 
@@ -1298,6 +1298,71 @@ int32_t emb_mean_fill(const emb_fill_entry_t* entries, int64_t count, const void
 /* Kernel launches the two entry points above have issued in this process,
  * counted where the kernels are launched.                                      */
 int32_t emb_stat_rows_launches(int64_t* count);
+
+/* ---- device DictConcat: one-hot, squish, masks and concat in one launch ------
+ * The first step of the world model's sequential scan and the head of the
+ * Encoder.  One launch serves
+ *   embodied/jax/nets.py:467-500  nn.DictConcat: per key available, mask, one_hot
+ *                                 or squish, the cast, mask again, reshape; then
+ *                                 concatenate
+ *   embodied/jax/nets.py:80-99    available with bdims
+ *   embodied/jax/nets.py:59-60    symlog(x) = sign(x) log1p(|x|)
+ *   dreamerv3/rssm.py:76-79       mask(action, ~reset) in front of and behind it
+ *   dreamerv3/rssm.py:97          the same DictConcat in RSSM.imagine
+ *   dreamerv3/rssm.py:137         action /= sg(max(1, |action|))
+ *   dreamerv3/rssm.py:216-220     DictConcat(vspace, 1, squish=symlog) of the Encoder
+ * in place of twenty to thirty torch launches for a dict of two keys.
+ *
+ * `out` is (rows, width), EMB_F32 or EMB_BF16, its rows `out_stride` elements
+ * apart (a column slice of a wider matrix is out_stride > width).  Entry k is a
+ * contiguous (rows, elements) device array `x` of dtype EMB_F32, EMB_BF16,
+ * EMB_I32, EMB_I64, EMB_U8 or EMB_BOOL that fills the columns [first, first +
+ * span) of every row; the spans of the table tile [0, width) in any order.
+ * Per row r and key k
+ *   m = every element of x[r] != -inf (EMB_F32, EMB_BF16: a NaN is there) or
+ *       != -1 (EMB_I32, EMB_I64); always for EMB_U8 and EMB_BOOL
+ *   EMB_DICT_ONEHOT  span = elements * classes, column first + e * classes + c is
+ *                    1 where m and x[r, e] == c, else 0.  The index is compared,
+ *                    never used as an address: one outside [0, classes) gives
+ *                    zeros (jax.nn.one_hot), and an EMB_I64 value beyond the
+ *                    int32 range is outside, it is not wrapped (the reference's
+ *                    astype(int32) never sees one: JAX runs without x64).
+ *   EMB_DICT_NONE    span = elements, column first + e is x[r, e] as float32
+ *                    where m, else 0
+ *   EMB_DICT_SYMLOG  the same of sign(x) log1p(|x|)
+ * `reset` (NULL: none) is one byte per row, uint8 or bool: a row whose byte is
+ * not 0 is written as zeros (both masks of rssm.py:76-79).  With `unit` != 0
+ * every continuous value v is stored as v / max(1, |v|) (rssm.py:137); one-hot
+ * values pass.  Arithmetic is float32, rounded once at the store: the reference
+ * divides after rounding, and for every finite v the two give the same bits
+ * (|v| <= 1 stores the rounded v, anything else +-1).
+ * No atomics: the same bits run to run.  16-byte stores wherever a row's own
+ * address allows, element stores before and behind them.
+ * EMB_ERR_INVALID before any HIP call, rows = 0 included: count outside
+ * 1 .. EMB_DICT_MAX_KEYS, a NULL `table`, `out` or `x`, an unknown dtype or
+ * kind, elements < 1, classes outside 1 .. 16 384, one-hot of a float input,
+ * squish of an integer input, an address off its element size, spans that
+ * overlap or do not tile [0, width), width outside 1 .. 16 384, out_stride <
+ * width, rows < 0 or rows * out_stride > 2^31 - 1.  rows = 0: EMB_OK, nothing
+ * is launched.                                                                */
+#define EMB_DICT_ONEHOT 0
+#define EMB_DICT_NONE 1
+#define EMB_DICT_SYMLOG 2
+#define EMB_DICT_MAX_KEYS 16
+typedef struct emb_dict_entry {
+  const void* x;
+  int32_t dtype;    /* EMB_F32, EMB_BF16, EMB_I32, EMB_I64, EMB_U8, EMB_BOOL */
+  int32_t kind;     /* EMB_DICT_*                                          */
+  int32_t elements; /* per row                                             */
+  int32_t classes;  /* EMB_DICT_ONEHOT only                                */
+  int32_t first;    /* the key's first output column                       */
+  int32_t reserved;
+} emb_dict_entry_t;
+int32_t emb_dict_concat(const emb_dict_entry_t* table, int64_t count, int64_t rows, int64_t width, void* out,
+                        int64_t out_stride, int32_t out_dtype, const void* reset, int32_t unit, void* stream);
+/* Kernel launches emb_dict_concat has issued in this process, counted where the
+ * kernel is launched.                                                          */
+int32_t emb_dict_concat_launches(int64_t* count);
 
 /* ----------------------------------------------------------- collectives --
  * The two exchange steps of the sharded path on RCCL directly (xGMI inside one
