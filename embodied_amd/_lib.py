@@ -320,6 +320,8 @@ SIGNATURES = {
     'emb_direct_alltoall': [p, p, p, i64, p],
     'emb_direct_exchange': [p, p, p, p, i64, p, i64, i32, i32],
     'emb_copy_bytes': [p, p, i64, p],
+    'emb_host_register': [p, i64, p],
+    'emb_host_unregister': [p],
     'emb_mask_actions_notify': [p, p, i64, i64, i32, p, p, p, C.c_uint32, p],
     'emb_stream_create_on_cus': [i32, i32, p],
     'emb_stream_destroy': [p],

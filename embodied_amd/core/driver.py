@@ -7,7 +7,9 @@ Three ways to run the same loop:
   stack, numpy mask, per-env callbacks (BASELINE config "numpy Driver on CPU").
 * `Driver(fns, device='cuda')` — per-env observations are written into a pinned
   (N, S) slab (by the env processes themselves with `parallel=True`: one shared,
-  HIP-registered block), uploaded -- in pieces, under the slower workers' steps,
+  HIP-registered block -- or, where the runtime cannot register existing memory,
+  a shared block copied piece by piece into an allocated pinned one), uploaded
+  -- in pieces, under the slower workers' steps,
   by a kernel that reads the pinned memory -- and handed to the policy as device
   tensors; the action mask (`emb_mask_actions`) runs on the GPU and its stores
   bring the next step's actions down to pinned host memory; the build's own
@@ -31,6 +33,7 @@ sets of device buffers: a policy that keeps `obs` (or a reader of
 `Driver(..., fresh_obs=True)` switches the rotation off;
 a device vector env (`batch_env=`) owns its outputs and states its own rule.
 """
+import ctypes
 import multiprocessing as mp
 import os
 from multiprocessing import shared_memory
@@ -146,6 +149,7 @@ class Driver:
     self.batch_env = batch_env
     self.parallel = parallel and batch_env is None
     self._upload_src, self._upload_ring, self._upload_turn = None, [], 0
+    self._upload_shared = None     # the workers' slab where `_upload_src` is a pinned copy of it
     self._acts_on_host, self._acts_pinned, self._acts_landed = None, {}, None
     self._acts_flag, self._acts_flag_want, self._acts_seq = None, 0, 0
     if batch_env is not None:
@@ -283,7 +287,8 @@ class Driver:
     """Env workers write their observations straight into one shared (N, ...)
     slab per key instead of pickling ~S bytes per env per step through a pipe
     (driver.py:17-25,61-62).  In device mode the slab is registered with the
-    HIP runtime, so it is also the pinned source of the upload."""
+    HIP runtime, so it is also the pinned source of the upload (a runtime that
+    refuses gets an allocated pinned block as the source instead)."""
     self.pipes[0].send(('obs_space',))
     try:
       space = self._receive(self.pipes[0])
@@ -309,12 +314,20 @@ class Driver:
     layout = {k: tuple(v) for k, v in layout.items()}
     if self.device is not None:
       whole = torch.from_numpy(np.ndarray(total, np.uint8, buffer=block.buf))
-      if torch.cuda.cudart().cudaHostRegister(whole.data_ptr(), total, 0) == 0:
+      registered = ctypes.c_int32(0)
+      api.emb_host_register(whole.data_ptr(), total, ctypes.byref(registered))
+      if registered.value:
         self._registered = getattr(self, '_registered', []) + [whole.data_ptr()]
+        self._upload_src = whole
+      else:
+        # Where the HIP runtime cannot pin memory the process already has, the
+        # upload reads a pinned block of the same layout that torch allocates;
+        # each piece of the slab is copied into it first (`_upload_piece`).
+        self._upload_shared = whole
+        self._upload_src = torch.empty(total, dtype=torch.uint8).pin_memory()
       # Four device copies used in turn (like a vector env's own output ring)
       # while nobody but the Replay sink sees them (`_rotate`); fresh ones otherwise.
       self._upload_layout = layout
-      self._upload_src = whole
       self._upload_ring, self._upload_turn = [], 0
       for _ in range(4):
         dev = torch.empty(total, dtype=torch.uint8, device=self.device)
@@ -369,8 +382,9 @@ class Driver:
     elif self.parallel:
       [proc.kill() for proc in self.procs]
       for ptr in getattr(self, '_registered', []):
-        torch.cuda.cudart().cudaHostUnregister(ptr)
+        api.emb_host_unregister(ptr)
       self._registered = []
+      self._upload_shared = None
       blocks = []
       for b, _ in list(getattr(self, '_shared', {}).values()) + list(getattr(self, '_act_slab', {}).values()):
         if not any(b is seen for seen in blocks):
@@ -775,6 +789,10 @@ class Driver:
     call here, five of them per step were slower than one (profiles/
     r06_ab_hostenvs.txt); the single whole-slab copy stays with the DMA engines."""
     _, _, dst, src = piece
+    if self._upload_shared is not None:
+      # (the pinned block was last read by the upload `_wait_uploads` has waited for)
+      at = src.storage_offset()
+      src.copy_(self._upload_shared[at: at + src.numel()])
     if self._upload_by_kernel:
       fast.emb_copy_bytes(src.data_ptr(), dst.data_ptr(), src.numel(), _lib.raw_stream(self.device))
     else:
@@ -808,7 +826,7 @@ class Driver:
         plan += [(0, n, a, b) for a, b in ((0, at), (at + nbytes, total)) if b > a]
       self._upload_plan = plan
       self._upload_pieces = {}
-      self._upload_by_kernel = len(plan) > 1 and bool(getattr(self, '_registered', None))
+      self._upload_by_kernel = len(plan) > 1
     if self._rotate():
       self._upload_turn = turn = (self._upload_turn + 1) & 3
       dev, self._upload_views = self._upload_ring[turn]

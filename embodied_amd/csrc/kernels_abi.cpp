@@ -85,6 +85,24 @@ int32_t emb_copy_bytes(const void* src, void* dst, int64_t bytes, void* stream) 
   });
 }
 
+int32_t emb_host_register(void* ptr, int64_t bytes, int32_t* registered) {
+  return guarded([&] {
+    need(ptr && bytes > 0 && registered, "host_register: bad arguments");
+    const hipError_t e = hipHostRegister(ptr, static_cast<size_t>(bytes), hipHostRegisterDefault);
+    // A refusal is an answer, not a failure: the runtime's error state is cleared,
+    // or the next kernel launch of this thread would report it as its own.
+    if (e != hipSuccess) (void)hipGetLastError();
+    *registered = e == hipSuccess ? 1 : 0;
+  });
+}
+
+int32_t emb_host_unregister(void* ptr) {
+  return guarded([&] {
+    need(ptr, "host_unregister: null pointer");
+    HIP_OK(hipHostUnregister(ptr));
+  });
+}
+
 int32_t emb_mask_actions(const void* act, void* out, int64_t n, int64_t row_elems, int32_t dtype,
                          const void* is_last, void* stream) {
   return guarded([&] {

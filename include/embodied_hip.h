@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 /* The library is built with hidden visibility: what this header declares is all
- * it exports (169 functions). */
+ * it exports (171 functions). */
 #if defined(__GNUC__)
 #pragma GCC visibility push(default)
 #endif
@@ -56,8 +56,9 @@ extern "C" {
  * emb_optim_grad_norms, emb_optim_adam_update, emb_slow_table, emb_slow_update,
  * emb_optim_update_slow, emb_optim_adam_update_slow, emb_pool_norm_act,
  * emb_pool_norm_act_grad, emb_norm_act_upsample, emb_norm_act_upsample_grad,
- * emb_conv_stage_launches, emb_dict_concat, emb_dict_concat_launches
- * (additions only).                                                         */
+ * emb_conv_stage_launches, emb_dict_concat, emb_dict_concat_launches,
+ * emb_host_register, emb_host_unregister
+ * (additions only).                                                       */
 #define EMB_ABI_VERSION 5
 
 #define EMB_OK 0
@@ -451,6 +452,16 @@ int32_t emb_mask_actions_notify(const void* act, void* out, int64_t n, int64_t r
  * through the DMA engines costs ~10 us of set-up per call on this system, a kernel
  * that reads across PCIe does not.  Any alignment.                              */
 int32_t emb_copy_bytes(const void* src, void* dst, int64_t bytes, void* stream);
+
+/* Page-locks and device-maps `bytes` of host memory the process already has (the
+ * Driver's shared observation slab, which its env processes write: what
+ * emb_copy_bytes then reads).  Not every system can do this to existing memory
+ * (a virtual machine's HIP runtime may refuse): *registered = 0 then, the status is
+ * EMB_OK and the runtime's error state is left clean -- the caller stages through
+ * pinned memory that it allocates instead.  emb_host_unregister for what
+ * was registered here only, before the memory goes away.                       */
+int32_t emb_host_register(void* ptr, int64_t bytes, int32_t* registered);
+int32_t emb_host_unregister(void* ptr);
 
 /* acts zeroed where is_last (driver.py:72-74,84-87): out = act * ~is_last as a
  * real multiply in `dtype`; act, out (n, row_elems), out may alias act.      */

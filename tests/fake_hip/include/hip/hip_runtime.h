@@ -18,7 +18,7 @@ typedef struct fakeStream* hipStream_t;
 struct fakeEvent { uint64_t recorded; };
 typedef fakeEvent* hipEvent_t;
 enum { hipEventDisableTiming = 2, hipStreamNonBlocking = 1, hipHostMallocDefault = 0,
-       hipDeviceMallocFinegrained = 1, hipMemcpyHostToDevice = 1 };
+       hipDeviceMallocFinegrained = 1, hipMemcpyHostToDevice = 1, hipHostRegisterDefault = 0 };
 enum { hipDeviceAttributeIsLargeBar = 1, hipDeviceAttributeMultiprocessorCount = 2 };
 struct dim3 { unsigned x, y, z; dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {} };
 
@@ -41,6 +41,8 @@ inline hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) { return fake_
 inline hipError_t hipExtMallocWithFlags(void** p, size_t bytes, unsigned) { return fake_alloc(p, bytes); }
 inline hipError_t hipFree(void* p) { std::free(p); return hipSuccess; }
 inline hipError_t hipHostFree(void* p) { std::free(p); return hipSuccess; }
+inline hipError_t hipHostRegister(void*, size_t, unsigned) { return hipSuccess; }
+inline hipError_t hipHostUnregister(void*) { return hipSuccess; }
 inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, int, hipStream_t) {
   std::memcpy(dst, src, bytes);
   return hipSuccess;

@@ -143,7 +143,7 @@ def test_header_declares_and_binding_covers_the_new_symbols():
   sources = __import__('embodied_amd.build', fromlist=['SOURCES']).SOURCES
   assert 'dict_concat.hip' in sources and 'dict_concat_abi.cpp' in sources
   count = len(declared_symbols())
-  assert count == 169 and f'it exports ({count} functions)' in text
+  assert count == 171 and f'it exports ({count} functions)' in text
   assert f'the C ABI ({count} entry points' in (ROOT / 'README.md').read_text()
   for name in ('ONEHOT', 'NONE', 'SYMLOG', 'MAX_KEYS'):
     assert int(re.search(r'#define\s+EMB_DICT_%s\s+(\d+)' % name, text).group(1)) == getattr(_lib, 'DICT_' + name)

@@ -41,6 +41,41 @@ def test_copy_bytes_from_pinned_host_memory(emb, nbytes, src_off, dst_off):
     _lib.api.emb_copy_bytes(None, twin.data_ptr(), 8, None)
 
 
+def test_host_register_pins_or_declines_and_leaves_no_error_behind(emb):
+  """`emb_host_register` on memory the process already has (the Driver's shared
+  slab): either it is pinned and a kernel reads it, or the runtime declines and
+  says so in `registered` -- and the launches that follow must not inherit the
+  runtime's error either way."""
+  from multiprocessing import shared_memory
+  from embodied_amd import _lib
+  nbytes = (64 << 10) + 256
+  block = shared_memory.SharedMemory(create=True, size=nbytes)
+  try:
+    host = np.ndarray(nbytes, np.uint8, buffer=block.buf)
+    host[:] = np.random.default_rng(3).integers(0, 256, nbytes, dtype=np.uint8)
+    registered = C.c_int32(-1)
+    _lib.api.emb_host_register(host.ctypes.data, nbytes, C.byref(registered))
+    assert registered.value in (0, 1)
+    dev = torch.zeros(nbytes, dtype=torch.uint8, device='cuda')
+    twin = dev.clone()                                        # torch checks the runtime's last error behind a launch
+    _lib.api.emb_copy_bytes(dev.data_ptr(), twin.data_ptr(), nbytes, _lib.raw_stream(dev.device))
+    torch.cuda.synchronize()
+    if registered.value:
+      _lib.api.emb_copy_bytes(host.ctypes.data, dev.data_ptr(), nbytes, _lib.raw_stream(dev.device))
+      assert np.array_equal(dev.cpu().numpy(), host)
+      _lib.api.emb_host_unregister(host.ctypes.data)
+    with pytest.raises(ValueError):
+      _lib.api.emb_host_register(None, nbytes, C.byref(registered))
+    with pytest.raises(ValueError):
+      _lib.api.emb_host_register(host.ctypes.data, nbytes, None)
+    with pytest.raises(ValueError):
+      _lib.api.emb_host_unregister(None)
+    del host
+  finally:
+    block.close()
+    block.unlink()
+
+
 @pytest.mark.parametrize('n,row_elems,dtype', [
     (64, 1, torch.int32), (64, 6, torch.float32), (7, 3, torch.bfloat16), (64, 17, torch.float64),
     (4096, 33, torch.float32)])               # the last one: 528 workgroups on one counter
