@@ -18,7 +18,8 @@ HERE = pathlib.Path(__file__).resolve().parent
 CSRC = HERE / 'csrc'
 OUT = HERE / 'libembodied_hip.so'
 OBJ = HERE / 'build'
-SOURCES = ['movers.hip', 'step.hip', 'scans.hip', 'synth_env.hip', 'direct_comm.hip', 'normalize.hip', 'ppo_targets.hip',
+SOURCES = ['movers.hip', 'step.hip', 'scans.hip', 'synth_env.hip', 'direct_comm.hip', 'normalize.hip', 'normalize_grid.hip',
+           'ppo_targets.hip',
            'dreamer_targets.hip', 'twohot.hip', 'onehot_kl.hip', 'policy_loss.hip', 'optim.hip',
            'norm_act.hip', 'gru_gate.hip', 'onehot_sample.hip', 'norm_act_abi.cpp', 'gru_gate_abi.cpp',
            'conv_stage.hip', 'conv_stage_abi.cpp',

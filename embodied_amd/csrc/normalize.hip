@@ -4,7 +4,9 @@
 // optionally, the normalised values.  Nothing returns to the host.
 //
 // Up to kNormLdsMax values keep their order-preserving integer keys in LDS; more
-// values are re-read from global memory by every pass of the same kernel.
+// values are re-read from global memory by every pass of the same kernel.  From
+// kNormGridMin values on a call goes to normalize_grid.hip instead; this kernel
+// stays what a captured stream without a scratch block gets at those sizes.
 #include "wave_util.h"          // LaunchCount
 #include "normalize_device.h"   // (float32 operations one by one: fp contract off)
 #include "norm_select.h"        // to_key, hist_add, the two-rank radix select
@@ -131,6 +133,14 @@ hipError_t launch_normalize(const float* x, int64_t n, float* state, int impl, b
                             const float* sub, float* out, hipStream_t stream) {
   const uint32_t flags = static_cast<uint32_t>(impl) | (update ? 4u : 0u) | (debias ? 8u : 0u);
   const uint32_t count = static_cast<uint32_t>(n);
+  if (n >= kNormGridMin && (update || out)) {     // the whole chip: normalize_grid.hip
+    int64_t launched = 0;
+    bool taken = false;
+    const hipError_t status = launch_normalize_grid(x, n, state, impl, update, debias, keep, rate, limit, lo, hi,
+                                                    sub, out, stream, &launched, &taken);
+    g_count.n.fetch_add(launched, std::memory_order_relaxed);
+    if (taken || status != hipSuccess) return status;
+  }
   if (n <= kNormLdsMax)
     hipLaunchKernelGGL(normalize_kernel<true>, dim3(1), dim3(kNormThreads), 0, stream, x, sub, out, state,
                        count, flags, keep, rate, limit, lo.k, hi.k, lo.frac, hi.frac);

@@ -1,5 +1,5 @@
 // emb_normalize: the running return normaliser, one kernel launch per call
-// (normalize.hip).  Its own translation unit: it needs nothing of the replay's
+// (normalize.hip) or, from kNormGridMin values on, a chain (normalize_grid.hip).  Its own translation unit: it needs nothing of the replay's
 // handles, rings or stream ordering.
 #include "abi_common.h"
 #include "normalize.h"

@@ -1,8 +1,10 @@
 """The running return normaliser (embodied/jax/utils.py:16-91) resident on the
 device: every call is ONE kernel launch (`emb_normalize`, csrc/normalize.hip)
-on the current torch stream -- batch statistics, EMA step, debiasing and, if
-asked for, the normalised values -- with no host synchronisation and no
-allocation.
+up to `GRID_MIN` values, and from there a chain of at most five launches over
+the whole chip (csrc/normalize_grid.hip), on the current torch stream -- batch
+statistics, EMA step, debiasing and, if asked for, the normalised values -- with
+no host synchronisation and no allocation of torch's (the library keeps one
+scratch block per stream for the chain).
 
 Single replica.  `distributed.Normalize` (torch ops, `comm=` / `group=`) stays the
 form that agrees the statistics across data-parallel ranks; the two exchange
@@ -18,6 +20,9 @@ from ._lib import fast
 _IMPLS = {'meanstd': _lib.NORM_MEANSTD, 'perc': _lib.NORM_PERC}
 # state words: mean | lo, sqrs | hi, corr, offset, scale
 _WORDS = {'meanstd': ('mean', 'sqrs'), 'perc': ('lo', 'hi')}
+# Values from which a call is a chain of launches over the whole chip
+# (csrc/normalize_grid.hip) instead of one launch of one workgroup: kNormGridMin.
+GRID_MIN = 131072
 
 
 def launches():
@@ -33,7 +38,8 @@ class DeviceNormalize:
   the state buffer: valid in stream order until the next call on this object,
   which overwrites them in place (clone them to keep a value).  Input that is not
   contiguous float32 is converted first with one torch op (an allocation and a
-  launch of torch's own); pass contiguous float32 to stay at one launch.
+  launch of torch's own); pass contiguous float32 to stay at one launch up to
+  `GRID_MIN` values (beyond: up to 5 for 'perc', 3 for 'meanstd', 1 without update).
   'none' returns (0.0, 1.0) and launches nothing."""
 
   def __init__(self, impl, rate=0.01, limit=1e-8, perclo=5.0, perchi=95.0, debias=True):

@@ -538,7 +538,9 @@ int32_t emb_abstract_traj(const void* reward, const void* cont, int64_t T, int64
 /* ---- running return normaliser, float32 on device -------------------------
  * The reference's Normalize (embodied/jax/utils.py:16-91: DreamerV3's retnorm /
  * valnorm / advnorm, the advantage normaliser of the PPO loss) for ONE replica,
- * as one kernel launch of one workgroup.  `state` is five float32 words of
+ * as one kernel launch of one workgroup up to kNormGridMin values (131072,
+ * csrc/normalize.h); beyond, the chain of launches described in
+ * csrc/normalize_grid.hip (below).  `state` is five float32 words of
  * DEVICE memory that the caller owns and zeroes once:
  *   [0] mean | lo   [1] sqrs | hi   [2] corr   [3] offset   [4] scale
  * update != 0: the running statistics take one EMA step
@@ -556,6 +558,25 @@ int32_t emb_abstract_traj(const void* reward, const void* cont, int64_t T, int64
  *   out[i] = (x[i] - (sub ? sub[i] : offset)) / scale     (out may be x)
  * Nothing returns to the host: no synchronisation, no allocation.  Up to 16384
  * values stay in LDS; more are re-read from global memory by the same launch.
+ * From kNormGridMin values on, a call with update or out is a chain over
+ * min(ceil(n / 4096), 256) workgroups, each on one contiguous tile of x, the
+ * phases ordered by the stream and no workgroup waiting for another: for PERC
+ * three histogram passes (11 / 11 / 10 key bits, the four ranks k_lo, k_lo + 1,
+ * k_hi, k_hi + 1 at once) and a one-workgroup finish, for MEANSTD one pass of
+ * per-workgroup float64 sums and the finish that adds them in index order, then
+ * the output pass: at most 5 kernels for PERC with out, 3 for MEANSTD with out,
+ * 1 with update = 0.  lo / hi are the bits of the one-workgroup kernel; the
+ * float64 sums are associated differently from it (per tile, then in tile
+ * order), so mean / sqrs may differ from it in the last float32 bit -- and are
+ * the same bits from run to run (no float atomics).
+ * Scratch of the chain: the library's own, one block per (device, stream) of
+ * about 60 KB (a double2 per workgroup and the three histogram levels),
+ * hipMalloc'ed on that stream's first large call and never freed before the
+ * process ends.  The histograms are cleared at the head of every PERC update
+ * (hipMemsetAsync; while the stream is being captured, a small kernel instead,
+ * one launch more), so a call that died half way cannot poison the next.  A
+ * stream that is being captured and has no block yet gets the one-workgroup
+ * kernel: nothing is allocated inside a capture.
  * EMB_ERR_INVALID before any launch: a NULL config / state (or x with n > 0),
  * n < 0, an unknown impl, rate outside [0, 1], a percentile outside [0, 100],
  * update with n = 0, sub without out.                                          */
